@@ -13,6 +13,11 @@ drop-in GaussianRasterizer (forward) + autograd backward with a fixed dL/dcolor,
 reference does at gs_renderer.py:144-152 and again inside loss.backward() (gs_trainer.py:287).
 With N GPUs every rank renders its own camera of the same Gaussian set (frames are independent: weak
 scaling); the only communication is the metric gather.  Rank 0 prints ONE JSON line on stdout.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps (with the sampled HIP-event timing of
+the dominant kernel that its `roofline` block reads) and the line.  --full adds everything else the line has carried: the box,
+host and memory figures, the measured copy peak, a per-stage pass, the two-frames-in-flight figure, the PMC figures from
+profiles/ and the CPU baseline.  --dump-outputs DIR writes what rank 0's last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -66,13 +71,22 @@ def parse_args():
     ap.add_argument("--frames-per-rank", type=int, default=1,
                     help="cameras each rank renders per step (frame f of rank r = camera r * K + f).  BASELINE configs[4] -- 8 frames x "
                          "300k Gaussians over 8 GPUs -- is `--gpus 8 --gaussians 300000 --frames-per-rank 1`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-two-streams", action="store_true", help="skip the secondary two-frames-in-flight figure")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline figure: box, host and memory figures, the measured "
+                         "copy peak, the per-stage pass, the two-frames-in-flight figure, the PMC figures from profiles/, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-two-streams", action="store_true", help="(--full) skip the secondary two-frames-in-flight figure")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget for the CPU baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last timed step computed (image, radii, the leaves' gradients) "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all (dump_outputs)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="ranks only rendezvous (gloo) and gather their ids -- no rasterizer work, no GPU needed; "
                          "checks the self-launcher (tests/test_bench_launcher.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def visible_gpu_count(sysfs="/sys/class/kfd/kfd/topology/nodes", devdir="/dev/dri", env=None):
@@ -293,6 +307,36 @@ def measured_copy_peak(torch, device, nbytes=1 << 30, reps=10):
     return rate(lib_copy), rate(lambda: b.copy_(a))
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, frames, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the outputs of the last timed step -- per frame of the step, {name: tensor} as the caller received them --
+    as out_dir/<name>.npy in float32 (radii are small integers: exact).  With several frames per step the names end in _frame<k>.
+    When the whole would exceed `limit`, every array keeps one fixed, seeded sample of its items, the same fraction for all: rows
+    (Gaussians) of the per-Gaussian arrays, pixels (columns of [3, H*W]) of the image.  The sample depends only on the shapes, so
+    the same arguments always keep the same items.  -> {name: shape written}"""
+    arrays = {}
+    for k, frame in enumerate(frames):
+        for name, v in frame.items():
+            arrays[name if len(frames) == 1 else f"{name}_frame{k}"] = v.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= limit else (limit - 4096 * len(arrays)) / total   # (4 KiB per file for the .npy header)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if frac < 1.0:
+            image = name.startswith("color")
+            items = a.reshape(a.shape[0], -1) if image else a   # [3, H*W]: a pixel is a column
+            n = items.shape[1] if image else items.shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * frac)), replace=False))
+            a = items[:, keep] if image else items[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = list(a.shape)
+    log(f"[dump-outputs] {len(written)} arrays to {out_dir}" + (f" (a seeded sample of {frac:.3f} of the items of each)" if frac < 1.0 else ""))
+    return written
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -314,7 +358,7 @@ def main():
     import torch
     import torch.distributed as dist
 
-    if rank == 0:
+    if rank == 0 and args.full:
         box_of_this_run()   # (asks rocm-smi for the GPU's id NOW: a child process, which must not be started once this process has touched the GPU)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback for the product path)")
@@ -385,14 +429,18 @@ def main():
         prefiltered=False, debug=False) for c in cams]
     settings = all_settings[0]
     leaves = list(t.values()) + [means2D]
+    named_leaves = dict(t, means2D=means2D)
 
-    def step():
+    def step(keep=None):
         for st_ in all_settings:   # this rank's K frames
             rast = GaussianRasterizer(raster_settings=st_)  # a new module per call, as the reference does
             color, radii = rast(means3D=t["means3D"], means2D=means2D, opacities=t["opacities"], shs=t["shs"],
                                 scales=t["scales"], rotations=t["rotations"])
             if not args.forward_only:
                 color.backward(dLd)
+            if keep is not None:   # (--dump-outputs: what this frame gave its caller, taken before the gradients are let go)
+                keep.append({"color": color, "radii": radii, **{"grad_" + k: v.grad for k, v in named_leaves.items() if v.grad is not None}})
+            if not args.forward_only:
                 for x in leaves:
                     x.grad = None
         return color, radii
@@ -428,16 +476,17 @@ def main():
     torch.cuda.reset_peak_memory_stats(device)
     fence()
     wait0 = _lib.hgs_debug_stat(b"forward_wait_ns")
-    cpu0, cg0 = time.process_time(), cgroup_cpu_stat()   # (process-wide user + system CPU seconds: every thread of this rank)
-    thr0 = thread_cpu_seconds()
+    cpu0, cg0 = time.process_time(), cgroup_cpu_stat() if args.full else {}   # (process-wide user + system CPU seconds: every thread of this rank)
+    thr0 = thread_cpu_seconds() if args.full else {}
+    last_step = [] if args.dump_outputs and rank == 0 else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        color, radii = step()
+    for i in range(args.steps):
+        color, radii = step(last_step if i == args.steps - 1 else None)
     host_issue_s = time.perf_counter() - t0   # (the loop without the final drain)
     fence()
     elapsed = time.perf_counter() - t0
-    cpu_seconds, cg1 = time.process_time() - cpu0, cgroup_cpu_stat()
-    thr1 = thread_cpu_seconds()
+    cpu_seconds, cg1 = time.process_time() - cpu0, cgroup_cpu_stat() if args.full else {}
+    thr1 = thread_cpu_seconds() if args.full else {}
     # which of rank 0's threads the CPU time went to (the main thread issues frames and waits for N; "pt_autograd_*" runs the backward node)
     threads_cpu = sorted(((n, round(t - thr0.get(tid, (n, 0.0))[1], 3)) for tid, (n, t) in thr1.items()), key=lambda x: -x[1])
     threads_cpu = [x for x in threads_cpu if x[1] >= 0.01][:8]
@@ -451,6 +500,9 @@ def main():
     coll_dev = device if backend == "nccl" else torch.device("cpu")  # where the tiny metric collectives run
     own_elapsed = elapsed   # this rank's own clock over the bracket (a straggler shows in per_rank_fps)
     elapsed = sharding.max_over_ranks(elapsed, coll_dev)
+    if last_step is not None:
+        dump_outputs(args.dump_outputs, last_step)
+        last_step = None
 
     # exact integers of this frame (shared with the oracle): N and the visible count
     N = dgr.last_frame_info()[0]
@@ -462,21 +514,23 @@ def main():
     frames = sharding.gather_frame_metrics([rank], [[float(N), float(Pv), float(device.index), 1.0, KF * args.steps / own_elapsed, host_busy_us,
                                                      cpu_seconds, float(len(os.sched_getaffinity(0)))]],
                                            world, device=coll_dev)
-    copy_peak, torch_copy_peak = measured_copy_peak(torch, device) if rank == 0 else (None, None)
+    copy_peak, torch_copy_peak = measured_copy_peak(torch, device) if rank == 0 and args.full else (None, None)
 
     # per-stage breakdown in a separate, untimed pass (every stage bracketed by events)
-    profile_enable()
-    for _ in range(10):
-        step()
-    torch.cuda.synchronize()
-    stages = {k: round(v[0] / 10.0, 4) for k, v in profile_read().items()}  # ms per frame (a stage may have >1 timed span)
-    profile_enable(())
+    stages = {}
+    if args.full:
+        profile_enable()
+        for _ in range(10):
+            step()
+        torch.cuda.synchronize()
+        stages = {k: round(v[0] / 10.0, 4) for k, v in profile_read().items()}  # ms per frame (a stage may have >1 timed span)
+        profile_enable(())
 
     # secondary figure (single process only): the same frames with two in flight on two HIP streams -- independent frames
     # (validation / animation loops, or the reference's separate human + scene renders) can overlap one frame's
     # latency-bound binning with another's VALU-bound blending.  `value` above stays the serial number.
     fps_two_streams = None
-    if world == 1 and not args.forward_only and not args.no_two_streams:
+    if args.full and world == 1 and not args.forward_only and not args.no_two_streams:
         # Every stream renders its OWN copy of the leaves, made on that stream: autograd creates a leaf's AccumulateGrad node on the stream
         # that is current when the leaf first enters a graph, and warns when a backward then runs on another one (round 5's leg shared the
         # default stream's leaves between the two side streams: the warning was in every driver run).
@@ -553,10 +607,6 @@ def main():
                    "N_per_frame_all_ranks": [int(x) for x in frames[:, 0].tolist()]},
         "roofline": {"bound": "hbm", "kernel": KERNEL_OF[dominant], "achieved": round(achieved, 2),
                      "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5),
-                     "peak_measured": round(copy_peak, 1), "frac_of_measured": round(achieved / copy_peak, 5),
-                     "peak_measured_how": "1 GiB device-to-device float4-per-thread copy kernel (hgs_copy_bandwidth) on this GPU in "
-                                          "this run, (read + write bytes) / time; peak_torch_copy = the same with Tensor.copy_",
-                     "peak_torch_copy": round(torch_copy_peak, 1),
                      "traffic": None, "algorithmic_bytes_per_launch": int(dom_B),
                      "avg_launch_ms": round(dom_ms, 4), "launches_timed": prof[dominant][1], "timed_every_nth_launch": every_nth,
                      "avg_launch_note": "HIP events on the launch stream around the kernel, inside the timed region; the event pair "
@@ -565,118 +615,127 @@ def main():
                              "they do ~256 pixel-splat evaluations per 40-byte list entry and are VALU bound (see "
                              "roofline_valu: pipes saturated at ~0.47 of peak issue, at the floor of their instruction mix) with HBM mostly idle; the per-Gaussian kernels (K1, K8) are the ones on the "
                              "HBM roofline (DESIGN.md section 4)"},
-        "whole_frame": {"algorithmic_bytes": int(frame_B), "GB_per_s": round(frame_B * fps / world / 1e9, 2),
-                        "frac_of_hbm_peak": round(frame_B * fps / world / 1e9 / HBM_PEAK_GBPS, 5),
-                        "frac_of_measured_peak": round(frame_B * fps / world / 1e9 / copy_peak, 5)},
-        "box": box_of_this_run(),
-        "host_busy_us_per_frame": round(host_busy_us, 1),
-        # the host side of N ranks on one box (every rank's own figures; rank 0 reads the cgroup the ranks share): CPU seconds are process-wide
-        # user + system time over the timed region, `cores_busy` = their sum over the region's wall time -- against the cgroup's quota
-        "ranks_host": {"host_busy_us_per_frame": [round(float(x), 1) for x in frames[:, 5].tolist()],
-                       "cpu_seconds": [round(float(x), 4) for x in frames[:, 6].tolist()],
-                       "cores_busy": round(float(frames[:, 6].sum()) / elapsed, 3), "wall_seconds": round(elapsed, 4),
-                       "rank0_threads_cpu_seconds": threads_cpu,
-                       "affinity_cpus_per_rank": [int(x) for x in frames[:, 7].tolist()], "cpus_total_requested": cpus_total or None,
-                       "cgroup": {"cpu_max": cgroup_cpu_max(), "nr_periods": cg1.get("nr_periods", 0) - cg0.get("nr_periods", 0),
-                                  "nr_throttled": cg1.get("nr_throttled", 0) - cg0.get("nr_throttled", 0),
-                                  "throttled_usec": cg1.get("throttled_usec", 0) - cg0.get("throttled_usec", 0)} if cg0 or cg1 else None},
-        "memory": {"peak_allocated_MB": round(peak_mem / 2**20, 1), "checkpoint_buffer_MB": None if ckpt_bytes is None else round(ckpt_bytes / 2**20, 1),
-                   "checkpoint_slots_used": ckpt_used},
-        "pixel_splat_evals_per_s": round(256.0 * N * (1 if args.forward_only else 2) * fps / world, 1),
-        "stages_ms": stages,
-        # the two per-Gaussian kernels are the ones on the HBM roofline: their algorithmic bytes
-        # (K1 = P (44 + 12 K) + 8 P + 67 P_v, K8 = P_v (111 + 12 K) + P (40 + 12 M)) over the live event timings
-        "stage_rooflines": {name: {"algorithmic_bytes": int(b), "GB_per_s": round(b / (stages[name] * 1e-3) / 1e9, 1),
-                                   "frac_of_hbm_peak": round(b / (stages[name] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                                   "frac_of_measured": round(b / (stages[name] * 1e-3) / 1e9 / copy_peak, 4)}
-                            for name, b in (("preprocess", P * (44 + 12 * K) + 8 * P + 67 * Pv),
-                                            ("preprocess_backward", Pv * (111 + 12 * K) + P * (40 + 12 * 16)))
-                            if stages.get(name) and not (args.forward_only and name == "preprocess_backward")},
-        "stage_rooflines_note": "preprocess also zeroes the backward's [P,12] gradient accumulator (48 B per Gaussian, fused into K1 instead of a memset "
-                                "launch): SURVEY 8d's K1 bytes do not count it -- `with_accumulator_zeroing` does (the WRITE_SIZE counter sees it: 1.9x the 8d writes)",
-        "stages_ms_note": "separate untimed pass with an event pair around EVERY stage: each pair costs a few microseconds of GPU "
-                          "time, so the sum exceeds ms_per_step",
+        "full": args.full,
     }
-    if "preprocess" in out["stage_rooflines"] and not args.forward_only:
-        b = P * (44 + 12 * K) + 8 * P + 67 * Pv + 48 * P
-        gb = b / (stages["preprocess"] * 1e-3) / 1e9
-        out["stage_rooflines"]["preprocess"]["with_accumulator_zeroing"] = {"bytes": int(b), "GB_per_s": round(gb, 1), "frac_of_hbm_peak": round(gb / HBM_PEAK_GBPS, 4),
-                                                                            "frac_of_measured": round(gb / copy_peak, 4)}
-    if fps_two_streams is not None:
-        out["two_frames_in_flight"] = {"value": round(fps_two_streams, 2), "unit": "frames/s",
-                                       "note": "same workload, frames alternate between two HIP streams of one process"}
+    if args.full:
+        out["roofline"].update({
+            "peak_measured": round(copy_peak, 1), "frac_of_measured": round(achieved / copy_peak, 5),
+            "peak_measured_how": "1 GiB device-to-device float4-per-thread copy kernel (hgs_copy_bandwidth) on this GPU in "
+                                 "this run, (read + write bytes) / time; peak_torch_copy = the same with Tensor.copy_",
+            "peak_torch_copy": round(torch_copy_peak, 1)})
+        out.update({
+            "whole_frame": {"algorithmic_bytes": int(frame_B), "GB_per_s": round(frame_B * fps / world / 1e9, 2),
+                            "frac_of_hbm_peak": round(frame_B * fps / world / 1e9 / HBM_PEAK_GBPS, 5),
+                            "frac_of_measured_peak": round(frame_B * fps / world / 1e9 / copy_peak, 5)},
+            "box": box_of_this_run(),
+            "host_busy_us_per_frame": round(host_busy_us, 1),
+            # the host side of N ranks on one box (every rank's own figures; rank 0 reads the cgroup the ranks share): CPU seconds are process-wide
+            # user + system time over the timed region, `cores_busy` = their sum over the region's wall time -- against the cgroup's quota
+            "ranks_host": {"host_busy_us_per_frame": [round(float(x), 1) for x in frames[:, 5].tolist()],
+                           "cpu_seconds": [round(float(x), 4) for x in frames[:, 6].tolist()],
+                           "cores_busy": round(float(frames[:, 6].sum()) / elapsed, 3), "wall_seconds": round(elapsed, 4),
+                           "rank0_threads_cpu_seconds": threads_cpu,
+                           "affinity_cpus_per_rank": [int(x) for x in frames[:, 7].tolist()], "cpus_total_requested": cpus_total or None,
+                           "cgroup": {"cpu_max": cgroup_cpu_max(), "nr_periods": cg1.get("nr_periods", 0) - cg0.get("nr_periods", 0),
+                                      "nr_throttled": cg1.get("nr_throttled", 0) - cg0.get("nr_throttled", 0),
+                                      "throttled_usec": cg1.get("throttled_usec", 0) - cg0.get("throttled_usec", 0)} if cg0 or cg1 else None},
+            "memory": {"peak_allocated_MB": round(peak_mem / 2**20, 1), "checkpoint_buffer_MB": None if ckpt_bytes is None else round(ckpt_bytes / 2**20, 1),
+                       "checkpoint_slots_used": ckpt_used},
+            "pixel_splat_evals_per_s": round(256.0 * N * (1 if args.forward_only else 2) * fps / world, 1),
+            "stages_ms": stages,
+            # the two per-Gaussian kernels are the ones on the HBM roofline: their algorithmic bytes
+            # (K1 = P (44 + 12 K) + 8 P + 67 P_v, K8 = P_v (111 + 12 K) + P (40 + 12 M)) over the live event timings
+            "stage_rooflines": {name: {"algorithmic_bytes": int(b), "GB_per_s": round(b / (stages[name] * 1e-3) / 1e9, 1),
+                                       "frac_of_hbm_peak": round(b / (stages[name] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                                       "frac_of_measured": round(b / (stages[name] * 1e-3) / 1e9 / copy_peak, 4)}
+                                for name, b in (("preprocess", P * (44 + 12 * K) + 8 * P + 67 * Pv),
+                                                ("preprocess_backward", Pv * (111 + 12 * K) + P * (40 + 12 * 16)))
+                                if stages.get(name) and not (args.forward_only and name == "preprocess_backward")},
+            "stage_rooflines_note": "preprocess also zeroes the backward's [P,12] gradient accumulator (48 B per Gaussian, fused into K1 instead of a memset "
+                                    "launch): SURVEY 8d's K1 bytes do not count it -- `with_accumulator_zeroing` does (the WRITE_SIZE counter sees it: 1.9x the 8d writes)",
+            "stages_ms_note": "separate untimed pass with an event pair around EVERY stage: each pair costs a few microseconds of GPU "
+                              "time, so the sum exceeds ms_per_step",
+        })
+        if "preprocess" in out["stage_rooflines"] and not args.forward_only:
+            b = P * (44 + 12 * K) + 8 * P + 67 * Pv + 48 * P
+            gb = b / (stages["preprocess"] * 1e-3) / 1e9
+            out["stage_rooflines"]["preprocess"]["with_accumulator_zeroing"] = {"bytes": int(b), "GB_per_s": round(gb, 1), "frac_of_hbm_peak": round(gb / HBM_PEAK_GBPS, 4),
+                                                                                "frac_of_measured": round(gb / copy_peak, 4)}
+        if fps_two_streams is not None:
+            out["two_frames_in_flight"] = {"value": round(fps_two_streams, 2), "unit": "frames/s",
+                                           "note": "same workload, frames alternate between two HIP streams of one process"}
 
-    # HBM traffic and VALU issue utilisation of the dominant kernel from the committed rocprofv3 PMC passes (separate
-    # runs of this same command; collected and corrected as MI355X_MICROARCH.md prescribes).  Attached only when they
-    # were taken on this workload AND on the kernel sources of the running build (profiles/build_id.py).
-    import glob
-    sys.path.insert(0, os.path.join(ROOT, "profiles"))
-    from build_id import csrc_sha16
-    here = csrc_sha16()
+        # HBM traffic and VALU issue utilisation of the dominant kernel from the committed rocprofv3 PMC passes (separate
+        # runs of this same command; FETCH_SIZE corrected as profiles/pmc_traffic.py states).  Attached only when they
+        # were taken on this workload AND on the kernel sources of the running build (profiles/build_id.py).
+        import glob
+        sys.path.insert(0, os.path.join(ROOT, "profiles"))
+        from build_id import csrc_sha16
+        here = csrc_sha16()
 
-    def newest(pattern, fits=None):
-        """the newest file of the pattern (named per round: r1p < r2a < r2b) -- with `fits`, the newest whose contents are of THIS workload (a
-        collection leaves one file per tracked workload: r6w_pmc_traffic.json, r6w_trained_pmc_traffic.json, ...), else the newest at all"""
-        files = sorted(glob.glob(os.path.join(ROOT, "profiles", pattern)))
-        if fits:
-            for cand in reversed(files):
-                try:
-                    if fits(json.load(open(cand))):
-                        return cand
-                except Exception:
-                    pass
-        return files[-1] if files else None
+        def newest(pattern, fits=None):
+            """the newest file of the pattern (named per round: r1p < r2a < r2b) -- with `fits`, the newest whose contents are of THIS workload (a
+            collection leaves one file per tracked workload: r6w_pmc_traffic.json, r6w_trained_pmc_traffic.json, ...), else the newest at all"""
+            files = sorted(glob.glob(os.path.join(ROOT, "profiles", pattern)))
+            if fits:
+                for cand in reversed(files):
+                    try:
+                        if fits(json.load(open(cand))):
+                            return cand
+                    except Exception:
+                        pass
+            return files[-1] if files else None
 
-    def of_this_workload(doc):
-        w = doc.get("workload") or {}
-        return (w.get("gaussians"), w.get("height"), w.get("width"), w.get("sh_degree")) == (P, H, W, D) and args.profile == w.get("profile", "uniform")
+        def of_this_workload(doc):
+            w = doc.get("workload") or {}
+            return (w.get("gaussians"), w.get("height"), w.get("width"), w.get("sh_degree")) == (P, H, W, D) and args.profile == w.get("profile", "uniform")
 
-    f = newest("*_pmc_traffic.json", of_this_workload)
-    if f:
-        pmc = json.load(open(f))
-        wl = pmc.get("workload", {})
-        same_wl = (wl.get("gaussians"), wl.get("height"), wl.get("width"), wl.get("sh_degree")) == (P, H, W, D)
-        if same_wl and pmc.get("csrc_sha16") == here and KERNEL_OF[dominant] in pmc["kernels"]:
-            out["roofline"]["traffic"] = pmc["kernels"][KERNEL_OF[dominant]]["hbm_bytes_corrected"]
-            out["roofline"]["traffic_source"] = "profiles/" + os.path.basename(f)
-        else:
-            out["roofline"]["traffic_note"] = (f"stale or other workload: profiles/{os.path.basename(f)} was taken on csrc "
-                                               f"{pmc.get('csrc_sha16')}, this build is {here}")
-    # The bound that holds for the blend kernels is VALU, reported as a roofline of its own (VERDICT r5, next #4):
-    #   achieved_frac  = wave-instructions (PMC) x 2 cycles (the guide's issue rate: one wave64 VALU instruction per SIMD every 2 cycles)
-    #                    / (1 024 SIMDs x kernel cycles)
-    #   mix_floor_frac = wave-instructions x the measured cost of THIS kernel's instruction mix (profiles/*_valu_mix.json: static histogram
-    #                    of its hot loop x profiles/r2_valu_model.txt) / 1 024 SIMDs / kernel time: ~1 = the kernel sits on what its mix allows
-    #   valu_pipe_busy_frac = SQ_ACTIVE_INST_VALU x 4 / (SIMDs x cycles): the pipes never idle -- NOT a fraction of peak issue
-    # Attached only for the workload and the kernel sources the counters were taken on.
-    f = newest("*_valu_utilization.json", of_this_workload)
-    if f:
-        vu_all = json.load(open(f))
-        vu = vu_all.get("kernels", {}).get(KERNEL_OF[dominant])
-        wl = vu_all.get("workload", {})
-        same_wl = (wl.get("gaussians"), wl.get("height"), wl.get("width"), wl.get("sh_degree")) == (P, H, W, D) and args.profile == wl.get("profile", "uniform")
-        if vu and vu_all.get("csrc_sha16") == here and same_wl:
-            instr, cycles = float(vu["valu_wave_instructions"]), float(vu["kernel_cycles"])
-            rv = {"bound": "valu", "kernel": KERNEL_OF[dominant], "wave_instructions_per_launch": instr, "kernel_cycles": cycles, "simds": 1024,
-                  "issue_peak": "one wave64 VALU instruction per SIMD every 2 cycles (MI355X_MICROARCH.md)",
-                  "achieved_frac": round(instr * 2.0 / (1024.0 * cycles), 4), "valu_pipe_busy_frac": vu["valu_busy_frac"],
-                  "source": "profiles/" + os.path.basename(f) + " (PMC: SQ_INSTS_VALU, SQ_ACTIVE_INST_VALU, GRBM_GUI_ACTIVE; separate rocprofv3 passes)"}
-            fm = newest("*_valu_mix.json")
-            if fm:
-                mix = json.load(open(fm))
-                mk = mix.get("kernels", {}).get(KERNEL_OF[dominant])
-                if mk and mix.get("csrc_sha16") == here:
-                    rv["mix_ns_per_instruction"] = mk["mix_ns_per_instruction"]
-                    rv["mix_floor_frac"] = round(instr * mk["mix_ns_per_instruction"] * 1e-9 / 1024.0 / (dom_ms * 1e-3), 4)
-                    rv["mix_source"] = "profiles/" + os.path.basename(fm) + f" ({mk['scope']}: " + ", ".join(f"{k} {v['share']:.0%}" for k, v in mk["classes"].items()) + ")"
-            out["roofline_valu"] = rv
-        else:
-            out["roofline_valu"] = {"bound": "valu", "kernel": KERNEL_OF[dominant], "achieved_frac": None,
-                                    "note": f"profiles/{os.path.basename(f)} was taken on csrc {vu_all.get('csrc_sha16')} / workload {wl}; this build is {here}, "
-                                            f"this run {P} Gaussians {W}x{H} degree {D} profile {args.profile}"}
+        f = newest("*_pmc_traffic.json", of_this_workload)
+        if f:
+            pmc = json.load(open(f))
+            wl = pmc.get("workload", {})
+            same_wl = (wl.get("gaussians"), wl.get("height"), wl.get("width"), wl.get("sh_degree")) == (P, H, W, D)
+            if same_wl and pmc.get("csrc_sha16") == here and KERNEL_OF[dominant] in pmc["kernels"]:
+                out["roofline"]["traffic"] = pmc["kernels"][KERNEL_OF[dominant]]["hbm_bytes_corrected"]
+                out["roofline"]["traffic_source"] = "profiles/" + os.path.basename(f)
+            else:
+                out["roofline"]["traffic_note"] = (f"stale or other workload: profiles/{os.path.basename(f)} was taken on csrc "
+                                                   f"{pmc.get('csrc_sha16')}, this build is {here}")
+        # The bound that holds for the blend kernels is VALU, reported as a roofline of its own (VERDICT r5, next #4):
+        #   achieved_frac  = wave-instructions (PMC) x 2 cycles (the CDNA4 issue rate: one wave64 VALU instruction per SIMD every 2 cycles)
+        #                    / (1 024 SIMDs x kernel cycles)
+        #   mix_floor_frac = wave-instructions x the measured cost of THIS kernel's instruction mix (profiles/*_valu_mix.json: static histogram
+        #                    of its hot loop x profiles/r2_valu_model.txt) / 1 024 SIMDs / kernel time: ~1 = the kernel sits on what its mix allows
+        #   valu_pipe_busy_frac = SQ_ACTIVE_INST_VALU x 4 / (SIMDs x cycles): the pipes never idle -- NOT a fraction of peak issue
+        # Attached only for the workload and the kernel sources the counters were taken on.
+        f = newest("*_valu_utilization.json", of_this_workload)
+        if f:
+            vu_all = json.load(open(f))
+            vu = vu_all.get("kernels", {}).get(KERNEL_OF[dominant])
+            wl = vu_all.get("workload", {})
+            same_wl = (wl.get("gaussians"), wl.get("height"), wl.get("width"), wl.get("sh_degree")) == (P, H, W, D) and args.profile == wl.get("profile", "uniform")
+            if vu and vu_all.get("csrc_sha16") == here and same_wl:
+                instr, cycles = float(vu["valu_wave_instructions"]), float(vu["kernel_cycles"])
+                rv = {"bound": "valu", "kernel": KERNEL_OF[dominant], "wave_instructions_per_launch": instr, "kernel_cycles": cycles, "simds": 1024,
+                      "issue_peak": "one wave64 VALU instruction per SIMD every 2 cycles (CDNA4)",
+                      "achieved_frac": round(instr * 2.0 / (1024.0 * cycles), 4), "valu_pipe_busy_frac": vu["valu_busy_frac"],
+                      "source": "profiles/" + os.path.basename(f) + " (PMC: SQ_INSTS_VALU, SQ_ACTIVE_INST_VALU, GRBM_GUI_ACTIVE; separate rocprofv3 passes)"}
+                fm = newest("*_valu_mix.json")
+                if fm:
+                    mix = json.load(open(fm))
+                    mk = mix.get("kernels", {}).get(KERNEL_OF[dominant])
+                    if mk and mix.get("csrc_sha16") == here:
+                        rv["mix_ns_per_instruction"] = mk["mix_ns_per_instruction"]
+                        rv["mix_floor_frac"] = round(instr * mk["mix_ns_per_instruction"] * 1e-9 / 1024.0 / (dom_ms * 1e-3), 4)
+                        rv["mix_source"] = "profiles/" + os.path.basename(fm) + f" ({mk['scope']}: " + ", ".join(f"{k} {v['share']:.0%}" for k, v in mk["classes"].items()) + ")"
+                out["roofline_valu"] = rv
+            else:
+                out["roofline_valu"] = {"bound": "valu", "kernel": KERNEL_OF[dominant], "achieved_frac": None,
+                                        "note": f"profiles/{os.path.basename(f)} was taken on csrc {vu_all.get('csrc_sha16')} / workload {wl}; this build is {here}, "
+                                                f"this run {P} Gaussians {W}x{H} degree {D} profile {args.profile}"}
 
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(g, cam, dL, H, W, D, args.cpu_seconds, not args.forward_only)
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(g, cam, dL, H, W, D, args.cpu_seconds, not args.forward_only)
     print(json.dumps(out), flush=True)
     if world > 1 or force_pg:
         dist.barrier()

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 # (the GPU's unique id, asked here -- no GPU process exists yet --: the python tools must not start rocm-smi once they have touched the GPU)
 export HGS_GPU_UNIQUE_ID=${HGS_GPU_UNIQUE_ID:-$(/opt/rocm/bin/rocm-smi --showuniqueid 2>/dev/null | sed -n 's/.*Unique ID: *0x\([0-9a-fA-F]*\).*/\1/p' | head -1)}
-COMMON="--gaussians 300000 --steps 400 --warmup 30 --no-cpu-baseline --no-two-streams"
+COMMON="--full --gaussians 300000 --steps 400 --warmup 30 --no-cpu-baseline --no-two-streams"
 python3 bench.py $COMMON > "$OUT/ranks1.json" 2> "$OUT/ranks1.err"
 for n in 2 4 8; do
   HGS_BENCH_BACKEND=gloo timeout 300 python3 bench.py --gpus $n $COMMON > "$OUT/ranks$n.json" 2> "$OUT/ranks$n.err"

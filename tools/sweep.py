@@ -28,7 +28,7 @@ def main():
     for P in (50_000, 100_000, 200_000, 300_000, 500_000, 1_000_000, 2_097_152):   # (the last: max_n_gaussians of hugs_scene.yaml:117)
         row = {"gaussians": P}
         for mode, flag in (("fwd", ["--forward-only"]), ("fwd_bwd", [])):
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gaussians", str(P), "--steps", "300", "--warmup", "40",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gaussians", str(P), "--steps", "300", "--warmup", "40",
                                 "--no-cpu-baseline", "--no-two-streams"] + flag, capture_output=True, text=True, timeout=600)
             if r.returncode != 0:
                 raise SystemExit(f"bench.py failed for P={P} ({mode}), rc {r.returncode}:\n{r.stderr[-2000:]}")
@@ -42,7 +42,7 @@ def main():
     # library's heuristics, whose long-tile threshold such frames choose by how many lists it leaves (binning.hip, LONG_ONE_ROUND)
     out["smaller_frames"] = []
     for P, H, W in ((100_000, 720, 1280), (20_000, 540, 960), (60_000, 512, 512), (10_000, 256, 256)):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gaussians", str(P), "--height", str(H), "--width", str(W), "--steps", "300",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gaussians", str(P), "--height", str(H), "--width", str(W), "--steps", "300",
                             "--warmup", "40", "--no-cpu-baseline", "--no-two-streams"], capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             raise SystemExit(f"bench.py failed for P={P} {W}x{H}, rc {r.returncode}:\n{r.stderr[-2000:]}")
@@ -51,7 +51,7 @@ def main():
                                       "fwd_bwd": {"fps": d["value"], "ms": d["ms_per_step"], "host_busy_us": d.get("host_busy_us_per_frame"), "stages_ms": d["stages_ms"]}})
         print(f"P={P} {W}x{H}: fwd+bwd {d['value']:.0f} FPS", file=sys.stderr)
     # (round 4) the trained-scene profile: 200 000 scene + 110 210 human Gaussians, surfaces / heavy-tailed sizes / reset opacities
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--profile", "trained", "--steps", "300", "--warmup", "40",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--profile", "trained", "--steps", "300", "--warmup", "40",
                         "--no-cpu-baseline", "--no-two-streams"], capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
         raise SystemExit(f"bench.py --profile trained failed, rc {r.returncode}:\n{r.stderr[-2000:]}")

@@ -1,7 +1,7 @@
 // Per-tile alpha blending: forward (K6) and pixel-side backward (K7).  SURVEY.md A.4 / A.5.
 //
 // CDNA4 design (not the CUDA shape):
-//  * No LDS staging, no barrier: the splat record of a list entry is the same for every lane, so it is fetched
+//  * No LDS staging of records, no barrier: the splat record of a list entry is the same for every lane, so it is fetched
 //    through the scalar data cache (s_load_dwordx8 from the constant address space) straight into SGPRs and
 //    used as a scalar operand of the VALU math.
 //  * Coverage culling: the tile-sort kernel leaves, for every tile, five compacted lists -- the entries that can
@@ -20,9 +20,10 @@
 //    everything composited behind the entry dotted with dL/dpixel; per Gaussian nine RAW sums are accumulated (moments
 //    of u = alpha_uncapped dL/dalpha, and the colour sums) -- the per-Gaussian factors are applied once per Gaussian by
 //    preprocess_backward_kernel.  The nine partial sums of all covered quads are added in registers, so there is one
-//    cross-lane reduction per (tile, entry) -- a transpose-reduce on gfx950's v_permlane32_swap / v_permlane16_swap
-//    plus DPP adds that leaves the nine totals in nine lanes -- and ONE global_atomic_add_f32 instruction into a
-//    contiguous [P][12] accumulator record.
+//    cross-lane reduction per (tile, entry) -- a transpose through a wave-private LDS region (the lane exchanges run on
+//    the LDS pipe, which the walk leaves idle otherwise; only the adds stay on the VALU) plus three DPP adds, and a DPP
+//    chain for the ninth sum, that leaves the nine totals in nine lanes -- and ONE global_atomic_add_f32 instruction
+//    into a contiguous [P][12] accumulator record.
 //
 // Compiled with -ffp-contract=off and -fno-slp-vectorize; the FMAs below are explicit so forward and backward
 // evaluate alpha with the identical instruction sequence (backward must re-take forward's skip decisions).
@@ -121,33 +122,12 @@ __device__ __forceinline__ float dpp_mov(float v)
 }
 constexpr int DPP_QUAD_XOR1 = 0xB1;  // quad_perm:[1,0,3,2]
 constexpr int DPP_QUAD_XOR2 = 0x4E;  // quad_perm:[2,3,0,1]
-constexpr int DPP_ROW_ROR8 = 0x128;  // lane i <- lane i^8 (rotate by half a row)
 constexpr int DPP_ROW_MIRROR = 0x140;       // lane i <- lane 15-i of its row
 constexpr int DPP_ROW_HALF_MIRROR = 0x141;  // lane i <- lane 7-i of its half-row
 
-// a and b are exchanged across the wave halves (W = 32) or across odd/even rows of 16 (W = 16) and added:
-// W = 32: lanes 0-31 get a[l] + a[l+32], lanes 32-63 get b[l-32] + b[l];
-// W = 16: rows 0 and 2 get a[row] + a[row+1], rows 1 and 3 get b[row-1] + b[row].
-typedef uint32_t swap_pair_t __attribute__((ext_vector_type(2)));
-template <int W>
-__device__ __forceinline__ float swap_add(float a, float b)
-{
-    const uint32_t ua = __builtin_bit_cast(uint32_t, a), ub = __builtin_bit_cast(uint32_t, b);
-    swap_pair_t r;
-    if constexpr (W == 32) r = __builtin_amdgcn_permlane32_swap(ua, ub, false, false);
-    else r = __builtin_amdgcn_permlane16_swap(ua, ub, false, false);
-    const uint32_t r0 = r.x, r1 = r.y;
-    return __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
-}
-
-// pairwise transpose-reduce step: afterwards lanes with `hi` clear hold (a + partner's a) and lanes
-// with `hi` set hold (b + partner's b); partner = lane ^ XOR within the quad.
-template <int CTRL>
-__device__ __forceinline__ float pair_step(float a, float b, bool hi)
-{
-    const float keep = hi ? b : a, send = hi ? a : b;
-    return keep + dpp_mov<CTRL>(send);
-}
+// The backward's per-wave LDS region for the cross-lane reduction: [entry of the pair][sum v0..v7][lane], 4 KB per wave,
+// 16 KB per 256-thread workgroup (no occupancy limit below 20 KB: profiles/r4_occupancy_lds.txt).  Waves never share it.
+constexpr int BWD_RED_FLOATS = 2 * 8 * 64;
 
 // Per-pixel backward state of one lane; a lane owns FOUR pixels, one in each 8x8 quad of the tile
 // (same (lx, ly) offset inside every quad), so that one wave covers the whole 16x16 tile.
@@ -207,7 +187,7 @@ __device__ __forceinline__ unsigned long long bwd_pixel(const SplatRec& s, uint3
     return took;
 }
 
-// NQ = 4: one wave per tile (four tiles per 256-thread workgroup, no LDS, no barrier).  A lane's four pixels sit in
+// NQ = 4: one wave per tile (four tiles per 256-thread workgroup, each wave with its own LDS region, no barrier).  A lane's four pixels sit in
 // the four quads, so the quad coverage mask of a list entry decides -- with scalar branches -- which of the
 // four per-pixel evaluations run at all, while the nine partial sums of ALL covered quads are added up in
 // registers before the single cross-lane reduction + atomic of that (tile, entry) pair.
@@ -227,7 +207,8 @@ __device__ __forceinline__ void
 blend_backward_wave(const Camera& cam, uint32_t lastg, int tile, int w, v2u range, const uint64_t* __restrict__ act,
                     size_t act_stride, const uint32_t* __restrict__ act_count, const Splat* __restrict__ splats,
                     const float* __restrict__ bg, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-                    const float* __restrict__ dL_dpix, float* __restrict__ grad_accum, const BwdSegment seg = BwdSegment{})
+                    const float* __restrict__ dL_dpix, float* __restrict__ grad_accum, float* red_all,
+                    const BwdSegment seg = BwdSegment{})
 {
     static_assert(!SEG || NQ == 1, "segments are per quad");
     const int lane = threadIdx.x & 63;
@@ -282,11 +263,14 @@ blend_backward_wave(const Camera& cam, uint32_t lastg, int tile, int w, v2u rang
     for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, d, 64));
     wmax = __builtin_amdgcn_readfirstlane(wmax);
     if (wmax == 0) return;
-    const bool b3 = lane & 8;
-    // which accumulator slot this lane's reduced value belongs to (see the reduction below); -1: none
-    const int half_row = lane >> 3;  // row = half_row >> 1, half = half_row & 1
-    const int slot_in_row[4] = {0, 2, 1, 3};
-    const int slot_of_lane = lane == 63 ? 8 : ((lane & 7) == 0 ? slot_in_row[half_row >> 1] + 4 * (half_row & 1) : -1);
+    // The reduction (see backward_entry): lane group g = lanes 8g..8g+7 sums v_g.  Lane 8g+i reads the eight partials of lanes
+    // 8i..8i+7 with two ds_read_b128; the odd groups read the two halves in the other order, which puts each b128 lane group
+    // (MI355X: four 16-lane groups, banks (a/4) mod 64) on 64 distinct banks.  Lane 8g adds total g into slot g of the
+    // Gaussian's record, lane 63 the blue total into slot 8.
+    float* const red = red_all + w * BWD_RED_FLOATS;
+    const int grp = lane >> 3;
+    const int rd = grp * 64 + (lane & 7) * 8 + (grp & 1) * 4;  // (floats) first read; the second at rd ^ 4
+    const int slot_of_lane = lane == 63 ? 8 : ((lane & 7) == 0 ? grp : -1);
 
     // entries of this tile that cover at least one quad (list 4), walked back to front; those beyond the deepest
     // position any pixel composited (pos1 > wmax) are skipped with a scalar branch
@@ -309,8 +293,11 @@ blend_backward_wave(const Camera& cam, uint32_t lastg, int tile, int w, v2u rang
     }
     const uint64_t* top = first + n;  // one past the deepest entry to visit
 
-    auto backward_entry = [&](const SplatRec& s, uint32_t val, uint32_t pos1) {
-        if (pos1 > wmax) return;
+    // Per entry: the pixel work, the eight sums v0..v7 stored to the entry's LDS buffer e at [v][lane] (four
+    // ds_write2st64_b32, conflict-free), and blue's DPP chain.  Returns whether any lane took the entry (else nothing was
+    // stored and no reduction or atomic is due).
+    auto backward_entry = [&](const SplatRec& s, uint32_t val, uint32_t pos1, int e, float& vb) -> bool {
+        if (pos1 > wmax) return false;
         float v[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         unsigned long long took = 0ull;  // lanes (of any quad) that took the splat: scalar
         if constexpr (NQ == 4) {
@@ -325,20 +312,12 @@ blend_backward_wave(const Camera& cam, uint32_t lastg, int tile, int w, v2u rang
             const float dy = s.y - p[0].pyf, bdy = s.B * dy, cdy = s.C * dy, q = __builtin_fmaf(-cdy, cdy, s.L);
             took = bwd_pixel(s, pos1, p[0], dy, bdy, q, v);
         }
-        if (took == 0ull) return;
-        // ---- transpose-reduce of v0..v7 over the wave: each step adds partner lanes AND halves the number of live
-        // registers.  Lane-half and row exchanges are gfx950's v_permlane{32,16}_swap (no select needed: the swap
-        // itself routes value a to one half and value b to the other), then one select step inside the row and three
-        // plain DPP adds.  Afterwards every lane of half-row (row r, half h) holds the total of slot_of_lane.
-        const float s0 = swap_add<32>(v[0], v[1]), s1 = swap_add<32>(v[2], v[3]);   // lanes 0-31: a, lanes 32-63: b
-        const float s2 = swap_add<32>(v[4], v[5]), s3 = swap_add<32>(v[6], v[7]);
-        const float t0 = swap_add<16>(s0, s1), t1 = swap_add<16>(s2, s3);           // rows: v0 v2 v1 v3 | v4 v6 v5 v7
-        float y = pair_step<DPP_ROW_ROR8>(t0, t1, b3);                              // lanes 0-7 of a row: t0, 8-15: t1
-        y += dpp_mov<DPP_ROW_HALF_MIRROR>(y);
-        y += dpp_mov<DPP_QUAD_XOR2>(y);
-        y += dpp_mov<DPP_QUAD_XOR1>(y);
+        if (took == 0ull) return false;
+        float* const buf = red + e * (8 * 64);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) buf[k * 64 + lane] = v[k];
         // v8 (blue): plain reduction; the classic gfx9 row broadcasts leave the wave total in row 3
-        float vb = v[8] + dpp_mov<DPP_QUAD_XOR1>(v[8]);
+        vb = v[8] + dpp_mov<DPP_QUAD_XOR1>(v[8]);
         vb += dpp_mov<DPP_QUAD_XOR2>(vb);
         vb += dpp_mov<DPP_ROW_HALF_MIRROR>(vb);
         vb += dpp_mov<DPP_ROW_MIRROR>(vb);
@@ -346,8 +325,31 @@ blend_backward_wave(const Camera& cam, uint32_t lastg, int tile, int w, v2u rang
         // rows untouched in ONE instruction; through the builtin it becomes v_mov 0 + v_mov_dpp + v_add.
         asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(vb));
         asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(vb));
-        // eight half-row leaders + lane 63 add the nine totals into the Gaussian's accumulator record with one
-        // atomic instruction
+        return true;
+    };
+    // The transposed read-back of buffer e: two ds_read_b128 per lane.  Scalar record loads share lgkmcnt and return out of
+    // order, so the only usable wait is lgkmcnt(0), which also waits for the records in flight: both entries of a pair are
+    // stored first, and only then is each read and finished -- the first wait comes two entries' pixel work after the loads
+    // it covers, the second waits for the one LDS read alone.  (Both reads in front of ONE wait hold 16 read registers at once:
+    // 68 VGPRs, seven waves per SIMD, and no faster in tools/microbench/bwd_reduce.hip.)  DS operations of a wave execute in
+    // order: a read needs no wait for the store before it, and a buffer's next store comes after the reads of it were consumed.
+    auto backward_read = [&](int e, float4& ra, float4& rb) {
+        const float* const buf = red + e * (8 * 64);
+        // (wave-scope fences: no instruction, they only keep the compiler from moving the reads above the stores)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        ra = *(const float4*)(buf + rd);
+        rb = *(const float4*)(buf + (rd ^ 4));
+    };
+    // Then each lane adds its eight partials, three in-half-row DPP adds finish group g's total in every lane of the
+    // group, and the eight group leaders + lane 63 add the nine totals into the Gaussian's accumulator record with one atomic
+    // instruction (nine distinct addresses).
+    auto backward_finish = [&](uint32_t val, const float4& ra, const float4& rb, float vb) {
+        float y = ((ra.x + ra.y) + (ra.z + ra.w)) + ((rb.x + rb.y) + (rb.z + rb.w));
+        y += dpp_mov<DPP_QUAD_XOR1>(y);
+        y += dpp_mov<DPP_QUAD_XOR2>(y);
+        y += dpp_mov<DPP_ROW_HALF_MIRROR>(y);
         if (slot_of_lane >= 0) atomicAdd(grad_accum + (size_t)(val & GID_MASK) * 12u + slot_of_lane, lane == 63 ? vb : y);
     };
 
@@ -365,13 +367,19 @@ blend_backward_wave(const Camera& cam, uint32_t lastg, int tile, int w, v2u rang
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
         const SplatRec rB0 = load_rec(splats, eB.z, lastg), rB1 = load_rec(splats, eB.x, lastg);
         const v4u eA2 = load_pair(top - 6 - j, 0);
-        backward_entry(rA0, eA.z, eA.w);
-        if (j + 1 < n) backward_entry(rA1, eA.x, eA.y);
+        float4 r00, r01, r10, r11;
+        float vb0, vb1;
+        const bool tA0 = backward_entry(rA0, eA.z, eA.w, 0, vb0);
+        const bool tA1 = j + 1 < n && backward_entry(rA1, eA.x, eA.y, 1, vb1);
+        if (tA0) backward_read(0, r00, r01), backward_finish(eA.z, r00, r01, vb0);
+        if (tA1) backward_read(1, r10, r11), backward_finish(eA.x, r10, r11, vb1);
         if (j + 2 >= n) break;
         rA0 = load_rec(splats, eA2.z, lastg), rA1 = load_rec(splats, eA2.x, lastg);
         const v4u eB2 = load_pair(top - 8 - j, 0);
-        backward_entry(rB0, eB.z, eB.w);
-        if (j + 3 < n) backward_entry(rB1, eB.x, eB.y);
+        const bool tB0 = backward_entry(rB0, eB.z, eB.w, 0, vb0);
+        const bool tB1 = j + 3 < n && backward_entry(rB1, eB.x, eB.y, 1, vb1);
+        if (tB0) backward_read(0, r00, r01), backward_finish(eB.z, r00, r01, vb0);
+        if (tB1) backward_read(1, r10, r11), backward_finish(eB.x, r10, r11, vb1);
         eA = eA2, eB = eB2;
     }
 }
@@ -394,7 +402,9 @@ blend_backward_kernel(Camera cam, uint32_t lastg, const uint2* __restrict__ rang
     const v2u range = ((const_u2p)ranges)[tile];
     if (range.y <= range.x) return;
     if (skip_from && range.y - range.x >= skip_from) return;  // a deep tile of a dense frame: the segmented kernel has it
-    blend_backward_wave<NQ>(cam, lastg, tile, w, range, act, act_stride, act_count, splats, bg, final_T, n_contrib, dL_dpix, grad_accum);
+    __shared__ float red[4 * BWD_RED_FLOATS];
+    blend_backward_wave<NQ>(cam, lastg, tile, w, range, act, act_stride, act_count, splats, bg, final_T, n_contrib, dL_dpix, grad_accum,
+                            red);
 }
 
 // Depth-segmented backward for SPARSE frames (a 512x512 human-only render, a person in front of an empty background): few
@@ -407,7 +417,8 @@ blend_backward_kernel(Camera cam, uint32_t lastg, const uint2* __restrict__ rang
 __device__ __forceinline__ void
 blend_backward_slot(uint32_t slot, const Camera& cam, uint32_t lastg, const uint2* __restrict__ ranges, const uint64_t* __restrict__ act,
                     size_t act_stride, const Splat* __restrict__ splats, const float* __restrict__ bg, const float* __restrict__ final_T,
-                    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ grad_accum, const Ckpt& ck)
+                    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix, float* __restrict__ grad_accum, const Ckpt& ck,
+                    float* red)
 {
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // (a dense frame's slots are packed, deep tiles only -- tile_scan_kernel --, and the grid may cover the layout's upper bound)
@@ -425,7 +436,7 @@ blend_backward_slot(uint32_t slot, const Camera& cam, uint32_t lastg, const uint
     seg.start = m + 1u < segs ? ck.state + (size_t)(first_slot + m) * 256u + w * 64 : nullptr;
     seg.end_state = ck.state + (size_t)(first_slot + segs - 1u) * 256u + w * 64;
     blend_backward_wave<1, true>(cam, lastg, (int)tile, w, range, act, act_stride, nullptr, splats, bg, final_T, n_contrib, dL_dpix,
-                                 grad_accum, seg);
+                                 grad_accum, red, seg);
 }
 
 __global__ void __launch_bounds__(256)
@@ -435,7 +446,8 @@ blend_backward_segmented_kernel(Camera cam, uint32_t lastg, const uint2* __restr
                                 const float* __restrict__ dL_dpix, float* __restrict__ grad_accum, Ckpt ck)
 {
     // (the grid is the frame's slot count, (N >> CKPT_SHIFT) + tiles)
-    blend_backward_slot(blockIdx.x, cam, lastg, ranges, act, act_stride, splats, bg, final_T, n_contrib, dL_dpix, grad_accum, ck);
+    __shared__ float red[4 * BWD_RED_FLOATS];
+    blend_backward_slot(blockIdx.x, cam, lastg, ranges, act, act_stride, splats, bg, final_T, n_contrib, dL_dpix, grad_accum, ck, red);
 }
 
 // A DENSE frame with deep tiles, both forms in ONE launch: the first dense_blocks workgroups are blend_backward_kernel<4>'s (four
@@ -457,11 +469,12 @@ blend_backward_mixed_kernel(Camera cam, uint32_t lastg, const uint2* __restrict_
                             const float* __restrict__ bg, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
                             const float* __restrict__ dL_dpix, float* __restrict__ grad_accum, Ckpt ck, uint32_t dense_blocks)
 {
+    __shared__ float red[4 * BWD_RED_FLOATS];  // (one region for both forms)
     if (blockIdx.x >= dense_blocks) {
         // (a dense frame's slots are packed, deep tiles only -- tile_scan_kernel --; the grid is their number when the host still
         //  knew it, else the layout's upper bound)
         blend_backward_slot(blockIdx.x - dense_blocks, cam, lastg, ranges, act, act_stride, splats, bg, final_T, n_contrib, dL_dpix,
-                            grad_accum, ck);
+                            grad_accum, ck, red);
         return;
     }
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -469,7 +482,8 @@ blend_backward_mixed_kernel(Camera cam, uint32_t lastg, const uint2* __restrict_
     if (tile >= cam.gx * cam.gy) return;
     const v2u range = ((const_u2p)ranges)[tile];
     if (range.y <= range.x || range.y - range.x >= CKPT_DEEP_MIN) return;
-    blend_backward_wave<4>(cam, lastg, tile, w, range, act, act_stride, act_count, splats, bg, final_T, n_contrib, dL_dpix, grad_accum);
+    blend_backward_wave<4>(cam, lastg, tile, w, range, act, act_stride, act_count, splats, bg, final_T, n_contrib, dL_dpix, grad_accum,
+                           red);
 }
 
 void launch_blend_backward(const Camera& cam, int P, const uint2* ranges, const uint64_t* act, size_t act_stride,

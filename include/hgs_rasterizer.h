@@ -437,7 +437,9 @@ size_t hgs_scratch_offset(const char *name, int32_t P, int64_t num_rendered, int
  * (result slots: forwards after which an unpolled deferred frame expires); host-time accounting since the library was loaded:
  * "forward_calls" / "forward_ns" (time inside hgs_rasterize_forward) / "forward_wait_ns" (the part of it spent waiting for N),
  * "backward_calls" / "backward_ns"; "binning_reruns" / "ckpt_reruns" (optimistically enqueued frames that were run again because
- * they needed more binning entries / checkpoint slots than guessed).  -1 for an unknown name. */
+ * they needed more binning entries / checkpoint slots than guessed); "last_forward_forms" / "last_backward_forms" (bit masks of the
+ * host-side launch forms the last forward / backward took: binning order, emit-scan, fused sort + blend, backward kernels, SH
+ * staging -- the bits are listed in hgs_api.hip).  -1 for an unknown name. */
 int64_t hgs_debug_stat(const char *name);
 
 /* The library reads its A/B switches (HGS_BIN_MODE, HGS_BWD_TWO_LAUNCHES, HGS_DEEP_FORWARD, HGS_LONG_MIN_SPARSE, HGS_LONG_MIN_DENSE, HGS_EMIT_SCAN, HGS_K1_STAGE_SH, HGS_BIG_PER_GROUP)

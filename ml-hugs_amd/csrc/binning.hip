@@ -2067,6 +2067,7 @@ void launch_tile_sort(const uint2* ranges, int num_tiles, const uint64_t* keys, 
             // (the shape's last frame had long lists but blended them with one wave per quad -- the scan's many_flat_long: a handful of
             //  workers stand by; should this frame decide otherwise they walk all of its items, slowly and with the same result)
             if (workers && hist.deep_blend == 0) workers = 8u;
+            note_forward_forms(workers ? FWD_DEEP_WORKERS : 0u);
             ka.cam = fb->cam, ka.lastg = fb->lastg, ka.splats = fb->splats, ka.bg = fb->bg, ka.out_color = fb->out_color, ka.final_T = fb->final_T;
             ka.n_contrib = fb->n_contrib, ka.clamp_output = fb->clamp_output, ka.ck = fb->ck, ka.num_workers = workers;
             if (workers) hipLaunchKernelGGL((tile_sort_small_kernel<true, true>), dim3(workers + num_tiles), dim3(256), 0, st, ka);

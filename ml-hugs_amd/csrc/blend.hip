@@ -99,6 +99,7 @@ void launch_blend_forward(const Camera& cam, int P, const uint2* ranges, const u
     const int tiles = cam.gx * cam.gy;
     const bool deep = deep_forward_enabled();
     const uint32_t workers = long_sorted && deep ? deep_workers_for(tiles) : 0u;
+    note_forward_forms(workers ? FWD_DEEP_WORKERS : 0u);
     if (!all_tiles && !deep) {
         // the repair of a wrong "no long tiles" guess without the depth-parallel path: every tile's workgroup starts and those
         // of the tiles that are not long leave at once (the host does not know which tiles are long)
@@ -500,6 +501,8 @@ void launch_blend_backward(const Camera& cam, int P, const uint2* ranges, const 
         uint32_t slots = (uint32_t)(num_rendered >> CKPT_SHIFT) + (uint32_t)num_tiles;   // (the sparse layout; a dense frame's upper bound)
         if (!sparse_frame && dense_slots >= 0 && (uint64_t)dense_slots < slots) slots = (uint32_t)dense_slots;
         const bool two_launches = switches().bwd_two_launches;   // (A/B measurements and the equivalence test)
+        note_backward_forms((sparse_frame || two_launches) && slots ? BWD_SEGMENTED : 0u);
+        note_backward_forms(sparse_frame ? 0u : two_launches ? BWD_TILE : BWD_MIXED);
         if ((sparse_frame || two_launches) && slots)
             hipLaunchKernelGGL(blend_backward_segmented_kernel, dim3(slots), dim3(256), 0, st, cam, (uint32_t)(P - 1), ranges, act,
                                act_stride, splats, bg, final_T, n_contrib, dL_dpix, grad_accum, ck);
@@ -511,12 +514,15 @@ void launch_blend_backward(const Camera& cam, int P, const uint2* ranges, const 
             hipLaunchKernelGGL(blend_backward_mixed_kernel, dim3(dense_blocks + slots), dim3(256), 0, st, cam, (uint32_t)(P - 1), ranges,
                                act, act_stride, act_count, splats, bg, final_T, n_contrib, dL_dpix, grad_accum, ck, dense_blocks);
         }
-    } else if (per_quad)
+    } else if (per_quad) {
+        note_backward_forms(BWD_QUAD);
         hipLaunchKernelGGL(blend_backward_kernel<1>, dim3(num_tiles), dim3(256), 0, st, cam, (uint32_t)(P - 1), ranges, act,
                            act_stride, act_count, splats, bg, final_T, n_contrib, dL_dpix, grad_accum, 0u);
-    else
+    } else {
+        note_backward_forms(BWD_TILE);
         hipLaunchKernelGGL(blend_backward_kernel<4>, dim3((num_tiles + 3) / 4), dim3(256), 0, st, cam, (uint32_t)(P - 1), ranges,
                            act, act_stride, act_count, splats, bg, final_T, n_contrib, dL_dpix, grad_accum, 0u);
+    }
 }
 
 }  // namespace hgs

@@ -85,6 +85,34 @@ const hgs::Switches& hgs::switches()
 // for the other translation units (densify.hip, knn.hip): message behind hgs_last_error() on this thread
 void hgs::set_last_error(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg); }
 
+// The host-side forms the last forward / backward took (hgs_debug_stat "last_forward_forms" / "last_backward_forms"): what the
+// launch paths pick on the host, which the scan's device-side decisions (n_total, the result slot) do not show.  A bit is set
+// where the host picks the launch; the entry point publishes the frame's mask when it returns (the last call of any thread wins).
+//   forward:  FWD_BIN_BY_CELL / FWD_BIN_IN_ORDER  the LDS binning path (neither: the global count kernel)
+//             FWD_EMIT_SCAN     the tile scan folded into emit (emit_scan_kernel)
+//             FWD_FUSED         tile sort + forward blend in one kernel
+//             FWD_STANDALONE    the stand-alone forward blend ran (unfused frames, the repair of a wrong "no long tiles" guess)
+//             FWD_LONG_REPAIR   that repair ran
+//             FWD_K1_STAGED     the preprocess kernel staged its SH rows through LDS (HGS_K1_STAGE_SH=1)
+//             FWD_BIG_GROUPS    big splats got binning groups of their own (HGS_BIG_PER_GROUP > 0 on a grouped frame)
+//             FWD_DEEP_WORKERS  depth-parallel workers were launched in front of the tiles (the scan's n_total[8] says which lists they take)
+//   backward: BWD_TILE          blend_backward_kernel<4>, one wave per tile (alone, or the second of two launches)
+//             BWD_QUAD          blend_backward_kernel<1>, one wave per quad
+//             BWD_SEGMENTED     blend_backward_segmented_kernel (every tile of a sparse frame, or the first of two launches)
+//             BWD_MIXED         blend_backward_mixed_kernel (a dense frame's deep tiles and the rest in one launch)
+//             BWD_K8_COOP_SHIFT the per-Gaussian backward's coop_mode (2 bits: 1 stores the dL/dsh rows, 2 also loads the SH rows)
+namespace {
+thread_local uint32_t t_fwd_forms = 0, t_bwd_forms = 0;
+std::atomic<uint32_t> g_last_fwd_forms{0}, g_last_bwd_forms{0};
+struct FormsScope {   // RAII at the top of the two entry points: collects the frame's bits, publishes them on return
+    uint32_t& mine; std::atomic<uint32_t>& last;
+    FormsScope(uint32_t& m, std::atomic<uint32_t>& l) : mine(m), last(l) { mine = 0; }
+    ~FormsScope() { last.store(mine, std::memory_order_relaxed); }
+};
+}  // namespace
+void hgs::note_forward_forms(uint32_t bits) { t_fwd_forms |= bits; }
+void hgs::note_backward_forms(uint32_t bits) { t_bwd_forms |= bits; }
+
 namespace {
 
 #define HIP_TRY(expr)                                                                                    \
@@ -607,6 +635,8 @@ int64_t hgs_debug_stat(const char* name)
     if (!strcmp(name, "backward_ns")) return (int64_t)g_stat_bwd_ns.load();
     if (!strcmp(name, "binning_reruns")) return (int64_t)g_stat_binning_reruns.load();
     if (!strcmp(name, "ckpt_reruns")) return (int64_t)g_stat_ckpt_reruns.load();
+    if (!strcmp(name, "last_forward_forms")) return (int64_t)g_last_fwd_forms.load();
+    if (!strcmp(name, "last_backward_forms")) return (int64_t)g_last_bwd_forms.load();
     return -1;
 }
 
@@ -632,6 +662,7 @@ int64_t hgs_rasterize_forward(const hgs_forward_args* args, hgs_alloc_fn alloc, 
     if (!args || !alloc || !state) return fail(HGS_ERR_INVALID_ARGUMENT, "null argument");
     StatScope stat(g_stat_fwd_calls, g_stat_fwd_ns);
     FrameSwitches frame_switches;   // one snapshot of the A/B switches for everything this frame launches
+    FormsScope forms(t_fwd_forms, g_last_fwd_forms);
     const hgs_forward_args& a = *args;
     hipStream_t st = (hipStream_t)stream;
     Camera cam;
@@ -696,6 +727,8 @@ int64_t hgs_rasterize_forward(const hgs_forward_args* args, hgs_alloc_fn alloc, 
     if (const int forced = group ? switches().bin_mode : 0)
         bin_mode = (forced == 'c' && num_cells <= BIN_MAX_CELLS) ? BIN_BY_CELL : forced == 'o' ? BIN_IN_ORDER : bin_mode;
     uint32_t* cell_count = bin_mode == BIN_BY_CELL ? tile_count + cell_counters_at : nullptr;
+    note_forward_forms((bin_mode == BIN_BY_CELL ? FWD_BIN_BY_CELL : bin_mode == BIN_IN_ORDER ? FWD_BIN_IN_ORDER : 0u) |
+                       (group && big_per_group > 0 ? FWD_BIG_GROUPS : 0u));
 
     { ProfScope ps(HGS_STAGE_PREPROCESS, st);
       launch_preprocess(a, cam, splats, tiles_touched, bin_mode, bin_mode == BIN_BY_CELL ? cell_count : tile_count, cell_slot, run_start,
@@ -739,6 +772,7 @@ int64_t hgs_rasterize_forward(const hgs_forward_args* args, hgs_alloc_fn alloc, 
     const bool guess_no_long = a.expect_no_long_tiles != 0;
     // HGS_FUSED_SORT_BLEND=0: separate tile-sort and forward-blend kernels (A/B measurements); default: fused
     const bool fused = switches().fused_sort_blend;
+    note_forward_forms(fused ? FWD_FUSED : 0u);
     float* final_T = (float*)(image + il.final_T);
     uint32_t* n_contrib = (uint32_t*)(image + il.n_contrib);
     FusedBlend fb{cam, (uint32_t)(Ptot - 1), splats, a.s.bg, a.out_color, final_T, n_contrib, a.clamp_output != 0 ? 1 : 0, Ckpt{}};
@@ -763,6 +797,7 @@ int64_t hgs_rasterize_forward(const hgs_forward_args* args, hgs_alloc_fn alloc, 
           launch_tile_sort(ranges, num_tiles, (uint64_t*)(bin + bl.keys), (uint64_t*)(bin + bl.list), (uint64_t*)(bin + bl.scratch), act,
                            bl.act_stride, act_count, large_tiles, n_total, bin + bl.parts, (uint32_t)bl.max_parts, false, true, nullptr, FrameHistory{}, st); }
         STAGE_CHECK(dbg, st, "tile_sort (long tiles)");
+        note_forward_forms(FWD_LONG_REPAIR | FWD_STANDALONE);
         { ProfScope ps(HGS_STAGE_BLEND_FORWARD, st);
           launch_blend_forward(cam, Ptot, ranges, act, bl.act_stride, act_count, splats, a.s.bg, a.out_color, final_T, n_contrib, n_total,
                                a.clamp_output != 0, large_tiles, false, true, fb.ck, st); }
@@ -780,6 +815,7 @@ int64_t hgs_rasterize_forward(const hgs_forward_args* args, hgs_alloc_fn alloc, 
         uint64_t* list = (uint64_t*)(bin + bl.list);
         uint64_t* act = (uint64_t*)(bin + bl.act) + ACT_PAD;
         if (scan_pending) {   // (the first, optimistic enqueue of such a frame; a re-run after an overflow finds the scan's results in place)
+            note_forward_forms(FWD_EMIT_SCAN);
             { ProfScope ps(HGS_STAGE_EMIT_KEYS, st);
               launch_emit_scan(Ptot, cam, splats, run_start, bin_mode == BIN_BY_CELL ? order : nullptr, windows, group, big_per_group, keys, tile_count,
                                cell_count, cell_count ? num_cells + 1 : 0, ranges, cursor, n_total, large_tiles, seg_first_arg, cap32,
@@ -798,6 +834,7 @@ int64_t hgs_rasterize_forward(const hgs_forward_args* args, hgs_alloc_fn alloc, 
         STAGE_CHECK(dbg, st, fused ? "tile_sort + blend_forward" : "tile_sort");
         if (!fused) {
             // (when the long-tile sort was skipped, long tiles read as empty here: they are blended by the repair)
+            note_forward_forms(FWD_STANDALONE);
             { ProfScope ps(HGS_STAGE_BLEND_FORWARD, st);
               launch_blend_forward(cam, Ptot, ranges, act, bl.act_stride, act_count, splats, a.s.bg, a.out_color, final_T, n_contrib, n_total,
                                    a.clamp_output != 0, large_tiles, true, with_long_tiles, fb.ck, st); }
@@ -909,6 +946,7 @@ int32_t hgs_rasterize_backward(const hgs_backward_args* args, void* stream)
     if (!args) return fail(HGS_ERR_INVALID_ARGUMENT, "null argument");
     StatScope stat(g_stat_bwd_calls, g_stat_bwd_ns);
     FrameSwitches frame_switches;
+    FormsScope forms(t_bwd_forms, g_last_bwd_forms);
     const hgs_backward_args& a = *args;
     const hgs_forward_args& f = a.fwd;
     hipStream_t st = (hipStream_t)stream;

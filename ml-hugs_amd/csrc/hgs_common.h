@@ -218,6 +218,14 @@ struct BinningLayout {
 
 // kernels / launchers (defined in the .hip files)
 void set_last_error(const char* msg);  // hgs_api.hip
+// the host-side forms a frame's launches took (hgs_debug_stat "last_forward_forms" / "last_backward_forms"; bits: hgs_api.hip)
+void note_forward_forms(uint32_t bits);
+void note_backward_forms(uint32_t bits);
+enum : uint32_t {
+    FWD_BIN_BY_CELL = 1u << 0, FWD_BIN_IN_ORDER = 1u << 1, FWD_EMIT_SCAN = 1u << 2, FWD_FUSED = 1u << 3, FWD_STANDALONE = 1u << 4,
+    FWD_LONG_REPAIR = 1u << 5, FWD_K1_STAGED = 1u << 6, FWD_BIG_GROUPS = 1u << 7, FWD_DEEP_WORKERS = 1u << 8,
+    BWD_TILE = 1u << 0, BWD_QUAD = 1u << 1, BWD_SEGMENTED = 1u << 2, BWD_MIXED = 1u << 3, BWD_K8_COOP_SHIFT = 8,
+};
 
 // The A/B switches that launch paths consult, read from the environment ONCE (at the first frame) -- not with a getenv per launch;
 // hgs_reload_switches() (tests, A/B tools that flip them inside one process) reads them again.  Published as an immutable snapshot

@@ -458,6 +458,7 @@ void launch_preprocess(const hgs_forward_args& a, const Camera& cam, Splat* spla
                                                            160 * 1024) == hipSuccess;
         const size_t staged_total = ((bin_bytes + 15) & ~(size_t)15) + (size_t)((group + 63) / 64) * stage_bytes;
         if (wants_stage && big_lds_ok && group <= 832 && staged_total <= 160 * 1024) {
+            note_forward_forms(FWD_K1_STAGED);
             hipLaunchKernelGGL((preprocess_kernel<BIN_BY_CELL, true>), dim3((P + group - 1) / group), dim3(group), staged_total, st,
                                HGS_K1_ARGS, counters, cell_slot, nullptr, (float4*)a.grad_accum_to_zero, big_per_group);
         } else
@@ -475,10 +476,11 @@ void launch_preprocess(const hgs_forward_args& a, const Camera& cam, Splat* spla
                 (void)hipGetLastError();
             hipLaunchKernelGGL((preprocess_kernel<BIN_IN_ORDER, false, true>), dim3((P + group - 1) / group), dim3(group), TileHist<true>::bytes(cam.gx * cam.gy), st,
                                HGS_K1_ARGS, counters, nullptr, run_start, (float4*)a.grad_accum_to_zero, big_per_group);
-        } else if (wants_stage && group <= SH_STAGE_THREADS && staged_total <= (big_lds_ok ? 160 * 1024 : 64 * 1024))
+        } else if (wants_stage && group <= SH_STAGE_THREADS && staged_total <= (big_lds_ok ? 160 * 1024 : 64 * 1024)) {
+            note_forward_forms(FWD_K1_STAGED);
             hipLaunchKernelGGL((preprocess_kernel<BIN_IN_ORDER, true>), dim3((P + group - 1) / group), dim3(group), staged_total, st, HGS_K1_ARGS, counters, nullptr,
                                run_start, (float4*)a.grad_accum_to_zero, big_per_group);
-        else
+        } else
             hipLaunchKernelGGL(preprocess_kernel<BIN_IN_ORDER>, dim3((P + group - 1) / group), dim3(group), bin_bytes, st, HGS_K1_ARGS, counters, nullptr, run_start,
                                (float4*)a.grad_accum_to_zero, big_per_group);
     } else
@@ -882,6 +884,7 @@ void launch_preprocess_backward(const hgs_backward_args& a, const Camera& cam, c
     // 37.0 us per-thread / 32.0 store only / 39.4 load + store; degree 1: 38.3 / 25.5 / 27.9 -- the round trip through LDS
     // sits in front of the whole per-Gaussian computation)
     const int coop_mode = forced >= 0 ? forced : 1;
+    note_backward_forms(f.shs ? (uint32_t)(coop_mode & 3) << BWD_K8_COOP_SHIFT : 0u);
     const size_t stage_bytes = (f.shs && coop_mode) ? (size_t)256 * (3 * (cam.D + 1) * (cam.D + 1) + 1) * sizeof(float) : 0;  // [4 waves][64 rows][3 K + 1]
 #define HGS_K8_ARGS dim3(blocks), dim3(256), stage_bytes, st, P, cam, f.means3D, f.shs, f.opacities, f.scales, f.rotations, f.cov3D_precomp, in2,       \
                     f.s.viewmatrix, f.s.projmatrix, f.s.campos, splats, a.grad_accum, a.dL_dmeans2D, a.dL_dopacity, a.dL_dcolors, a.dL_dmeans3D,  \

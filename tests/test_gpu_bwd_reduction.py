@@ -40,7 +40,8 @@ def _set_form(form, monkeypatch):
     if form == "default":
         monkeypatch.delenv("HGS_BWD_WAVES_PER_TILE", raising=False)
     else:
-        monkeypatch.setenv("HGS_BWD_WAVES_PER_TILE", "4" if form == "per_tile" else "1")
+        # (blend.hip, launch_blend_backward: 1 = blend_backward_kernel<4>, one wave per tile; 4 = blend_backward_kernel<1>, one wave per quad)
+        monkeypatch.setenv("HGS_BWD_WAVES_PER_TILE", "1" if form == "per_tile" else "4")
     reload_switches(monkeypatch)
 
 

@@ -25,7 +25,7 @@
  * Below the three rasterizer entry points (and their helpers) the header declares the rows either side of the rasterizer
  * that the same library carries, each replacing a named function of the reference: densification statistics (f-1), K nearest
  * template vertices / SMPL LBS blends (f-2), learned-LBS skinning (f-2), distCUDA2 (f-4), the photometric loss l1 + SSIM
- * (f-5), SceneGS.forward (f-6), rotation_6d_to_matrix / matrix_to_quaternion (f-7).  Same conventions: device pointers,
+ * (f-5), SceneGS.forward (f-6), rotation_6d_to_matrix / matrix_to_quaternion (f-7), TriPlane.forward (f-8).  Same conventions: device pointers,
  * sizes, a stream, a negative HGS_ERR_* on failure with hgs_last_error() for the text.
  */
 #ifndef HGS_RASTERIZER_H
@@ -385,6 +385,27 @@ int32_t hgs_rotation_6d_to_matrix(int32_t n, const float *d6, float *matrix, voi
 int32_t hgs_rotation_6d_to_matrix_backward(int32_t n, const float *d6, const float *dL_dmatrix, float *dL_dd6, void *stream);
 int32_t hgs_matrix_to_quaternion(int32_t n, const float *matrix, float *quat, void *stream);
 int32_t hgs_matrix_to_quaternion_backward(int32_t n, const float *matrix, const float *dL_dquat, float *dL_dmatrix, void *stream);
+
+/* Row f-8 -- the statement that opens every human step, fused: replaces TriPlane.forward
+ * (/root/reference/hugs/models/modules/triplane.py:26-40, called at /root/reference/hugs/models/hugs_trimlp.py:206,408):
+ *   g = ((x - center) / scale + 0.5) * 2 - 1, three F.grid_sample(align_corners=True, bilinear, zeros padding) and the cat:
+ *   feat [n,3F], feat[i, p F + c] for the planes p = xy, xz, yz.
+ * res = (resX, resY, resZ).  The planes keep the reference's logical shapes -- plane_xy [F,resX,resY], plane_xz [F,resX,resZ],
+ * plane_yz [F,resY,resZ] -- and are addressed through strides[p] = (channel, row, column) in elements, so the reference's NCHW
+ * parameters and texel-major ones (torch.channels_last: channel stride 1, the fast form -- a texel's 32 channels are one 128-byte
+ * segment) run through the same kernels.  grid[..., 0] indexes a plane's LAST axis: on plane_xy x runs along the axis of size resY
+ * and y along resX; on plane_xz x along resZ, z along resX; on plane_yz y along resZ, z along resY.  A corner outside its plane
+ * contributes nothing forward and receives nothing backward.  F = 32 (the reference's configuration) is the one implemented form;
+ * every res >= 2; feat / dL_dfeat 16-byte aligned.  The forward is bit-reproducible. */
+int32_t hgs_triplane_forward(int32_t n, int32_t F, const int32_t res[3], const int64_t strides[3][3], float center, float scale,
+                             const float *x /* [n,3] */, const float *plane_xy, const float *plane_xz, const float *plane_yz,
+                             float *feat /* [n,3F] */, void *stream);
+/* Its backward, one kernel: dL_dplanes[p] (same strides as the plane, ZERO on entry: float atomics add into them, so their last
+ * bits depend on arrival order) and dL_dx [n,3] (needs `planes`; no atomics, bit-reproducible).  dL_dx, dL_dplanes and each
+ * dL_dplanes[p] may be NULL: that half is skipped. */
+int32_t hgs_triplane_backward(int32_t n, int32_t F, const int32_t res[3], const int64_t strides[3][3], float center, float scale,
+                              const float *x, const float *const planes[3], const float *dL_dfeat /* [n,3F] */,
+                              float *dL_dx, float *const dL_dplanes[3], void *stream);
 
 /* Message for the last negative return value on the calling thread. */
 const char *hgs_last_error(void);

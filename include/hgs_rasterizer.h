@@ -407,6 +407,47 @@ int32_t hgs_triplane_backward(int32_t n, int32_t F, const int32_t res[3], const 
                               const float *x, const float *const planes[3], const float *dL_dfeat /* [n,3F] */,
                               float *dL_dx, float *const dL_dplanes[3], void *stream);
 
+/* Row f-9 -- the three decoders that consume the triplane features, fused: replaces AppearanceDecoder, GeometryDecoder and
+ * DeformationDecoder (/root/reference/hugs/models/modules/decoders.py:24-111, called at
+ * /root/reference/hugs/models/hugs_trimlp.py:409-410,430).  One generic form covers them: a TRUNK of n_trunk Linear layers, each
+ * followed by exact GELU (0.5 x (1 + erf(x / sqrt 2)), torch's default nn.GELU), and n_heads HEADS off the last trunk activation, each
+ * one Linear with its own activation.  Weights are torch's Linear.weight [out, in] row-major with bias [out], float32; every layer
+ * and head has its own pointers.  fp32 in, fp32 out on the exact-f32 matrix instruction; only the heads are written.
+ * Supported: in_width a multiple of 32 up to 128; 1..3 trunk layers, all 64 or all 128 wide; 1..3 heads of at most 64 columns in
+ * all.  Anything else is rejected on the host with a message, before any launch.  x and every head output (and their gradients)
+ * must be 16-byte aligned.  n == 0 returns 0 untouched.  The forward is bit-reproducible. */
+enum { HGS_MLP_MAX_TRUNK = 3, HGS_MLP_MAX_HEADS = 3 };
+enum { HGS_MLP_ACT_NONE = 0, HGS_MLP_ACT_GELU = 1, HGS_MLP_ACT_SIGMOID = 2 };
+typedef struct hgs_mlp_desc {
+    int32_t in_width;
+    int32_t n_trunk;
+    int32_t trunk_width[HGS_MLP_MAX_TRUNK];
+    int32_t n_heads;
+    int32_t head_width[HGS_MLP_MAX_HEADS];
+    int32_t head_act[HGS_MLP_MAX_HEADS];          /* HGS_MLP_ACT_* */
+    const float *trunk_weight[HGS_MLP_MAX_TRUNK]; /* [trunk_width[l], l ? trunk_width[l-1] : in_width] */
+    const float *trunk_bias[HGS_MLP_MAX_TRUNK];
+    const float *head_weight[HGS_MLP_MAX_HEADS];  /* [head_width[k], trunk_width[n_trunk-1]] */
+    const float *head_bias[HGS_MLP_MAX_HEADS];
+} hgs_mlp_desc;
+/* Gradients of the parameters, shaped like them, ZERO on entry: float atomics add into them (one flush per workgroup), so their
+ * last bits depend on arrival order.  Any pointer may be NULL: that gradient is skipped. */
+typedef struct hgs_mlp_grads {
+    float *trunk_weight[HGS_MLP_MAX_TRUNK];
+    float *trunk_bias[HGS_MLP_MAX_TRUNK];
+    float *head_weight[HGS_MLP_MAX_HEADS];
+    float *head_bias[HGS_MLP_MAX_HEADS];
+} hgs_mlp_grads;
+int32_t hgs_mlp_forward(int32_t n, const hgs_mlp_desc *net, const float *x /* [n,in_width] */,
+                        float *const head_out[HGS_MLP_MAX_HEADS] /* [n,head_width[k]] each */, void *stream);
+/* Its backward, one kernel, no workspace: the hidden activations are recomputed per tile of points from x and the weights.
+ * dL_dhead[k] [n,head_width[k]] may be NULL: that head contributes nothing.  dL_dx [n,in_width] (written once per point by its own
+ * tile, no atomics: bit-reproducible) may be NULL, as may `grads` and each pointer in it.  Nothing asked for: nothing is launched. */
+int32_t hgs_mlp_backward(int32_t n, const hgs_mlp_desc *net, const float *x, const float *const dL_dhead[HGS_MLP_MAX_HEADS],
+                         float *dL_dx, const hgs_mlp_grads *grads, void *stream);
+/* Points per tile of the two kernels (a launch-shape fact for tests that want sizes around it; results do not depend on it). */
+int32_t hgs_mlp_tile(void);
+
 /* Message for the last negative return value on the calling thread. */
 const char *hgs_last_error(void);
 

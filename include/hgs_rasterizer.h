@@ -262,6 +262,27 @@ int32_t hgs_rasterize_backward(const hgs_backward_args *args, void *stream);
  * hgs_rasterize_backward refuses a state this call has not resolved (num_rendered < 0). */
 int64_t hgs_forward_poll(hgs_forward_state *state, int32_t block, void *stream);
 
+/* Accumulated-alpha and depth maps of a rendered frame, with gradients: three passes of their own over what the forward left in
+ * its scratch (sorted per-quad lists, splat records, final_T, n_contrib) -- no second render.  For a pixel, over exactly the colour
+ * pass's contributors i in its order, w_i = alpha_i T_i:
+ *   alpha = sum_i w_i (= 1 - final_T),    depth = sum_i w_i z_i   (z_i: view-space z; un-normalised, the background adds nothing;
+ *   depth / alpha is the caller's statement).  Both maps [1,H,W] float32, 0 where a pixel has no contributor.
+ * Call order on ONE stream:  hgs_rasterize_forward, hgs_maps_forward, ..., hgs_maps_backward, hgs_rasterize_backward, hgs_maps_finish.
+ *   hgs_maps_forward   `args` / `state`: the forward call's arguments and the state it returned (a deferred frame must have been
+ *                      resolved by hgs_forward_poll).  Either output may be NULL.
+ *   hgs_maps_backward  BEFORE hgs_rasterize_backward: ADDS into args->grad_accum -- the six raw moments of slots 0..5 and, into pad
+ *                      slot 9, g_z = sum_pixels w_i dL/ddepth; the blend backward only ever adds as well, so the two sum.  Gradient
+ *                      conventions are the colour backward's (straight-through alpha cap).  Either upstream map may be NULL (= 0).
+ *   hgs_maps_finish    AFTER hgs_rasterize_backward (which writes dL_dmeans3D whole): dL_dmeans3D[i] += grad_accum[i][9] *
+ *                      (V[2], V[6], V[10]), rows past P into seg2_dL_dmeans3D.  Every other gradient of the maps has already come
+ *                      out of hgs_rasterize_backward with the colour's.
+ * All three validate on the host (negative return, hgs_last_error()), return 0 without a launch when P + seg2.P == 0, and do nothing
+ * on a frame that did not fit its binning buffer. */
+int32_t hgs_maps_forward(const hgs_forward_args *args, const hgs_forward_state *state, float *out_alpha, float *out_depth,
+                         void *stream);
+int32_t hgs_maps_backward(const hgs_backward_args *args, const float *dL_dalpha, const float *dL_ddepth, void *stream);
+int32_t hgs_maps_finish(const hgs_backward_args *args, void *stream);
+
 /* Replaces _C.mark_visible: present[i] = (z_view(means3D[i]) > 0.2). */
 int32_t hgs_mark_visible(int32_t P, const float *means3D, const float *viewmatrix, uint8_t *present,
                          void *stream);

@@ -309,10 +309,22 @@ void launch_blend_forward(const Camera& cam, int P, const uint2* ranges, const u
                           const uint32_t* act_count, const Splat* splats, const float* bg, float* out_color,
                           float* final_T, uint32_t* n_contrib, const uint32_t* n_total, bool clamp_output,
                           const uint32_t* large_tiles, bool all_tiles, bool long_sorted, const Ckpt& ck, hipStream_t st);
-// grad_accum: [P][12] floats, zero on entry: mean2D.x, mean2D.y, conic xx, xy, yy, opacity, r, g, b, pad x3
+// grad_accum: [P][12] floats, zero on entry: mean2D.x, mean2D.y, conic xx, xy, yy, opacity, r, g, b, g_z (maps.hip: slot 9), pad x2
 void launch_blend_backward(const Camera& cam, int P, const uint2* ranges, const uint64_t* act, size_t act_stride,
                            const uint32_t* act_count, bool sparse_frame, const Splat* splats, const float* bg,
                            const float* final_T, const uint32_t* n_contrib, const float* dL_dpix, float* grad_accum,
                            const Ckpt& ck, int64_t num_rendered, int64_t dense_slots, hipStream_t st);   // dense_slots < 0: not known
+
+// Alpha and depth maps from a rendered frame's lists (maps.hip).  P counts both segments; either map pointer may be NULL.
+void launch_maps_forward(const Camera& cam, int P, const uint2* ranges, const uint64_t* act, size_t act_stride, const uint32_t* act_count,
+                         const Splat* splats, const uint32_t* n_contrib, const uint32_t* n_total, float* out_alpha, float* out_depth,
+                         hipStream_t st);
+// adds into grad_accum: the six raw moments into slots 0..5, g_z = sum w dL/ddepth into pad slot 9
+void launch_maps_backward(const Camera& cam, int P, const uint2* ranges, const uint64_t* act, size_t act_stride, const uint32_t* act_count,
+                          const Splat* splats, const float* final_T, const uint32_t* n_contrib, const uint32_t* n_total,
+                          const float* dL_dalpha, const float* dL_ddepth, float* grad_accum, hipStream_t st);
+// dL_dmeans3D[i] += grad_accum[i][9] * (V[2], V[6], V[10]); rows from P1 on go to seg2_dL_dmeans3D
+void launch_maps_finish(int P1, int P, const float* V, const float* grad_accum, const uint32_t* n_total, float* dL_dmeans3D,
+                        float* seg2_dL_dmeans3D, hipStream_t st);
 
 }  // namespace hgs

@@ -581,7 +581,16 @@ class _RasterizeGaussians(torch.autograd.Function):
                     torch.cuda.set_device(prev_dev)
             if rc < 0:
                 _raise_last(lib, "rasterize_gaussians_backward")
+        return _RasterizeGaussians._input_grads(ctx, slab, saved)
 
+    @staticmethod
+    def _input_grads(ctx, slab, saved):
+        """What backward() returns: views of the gradient slab in the order of forward's inputs."""
+        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, _radii = saved[:8]
+        sec = saved[8:]
+        P1, M, P2, M2 = ctx.dims
+        P = P1 + P2
+        none_second = (None,) * ctx.n_second_inputs
         v = lambda k, *shape: _grad_view(slab, ctx.dims, k, *shape)
         # order of forward's inputs: means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
         # cov3Ds_precomp, raster_settings, clamp_output [, the second set in the same order without means2D]
@@ -603,6 +612,83 @@ class _RasterizeGaussians(torch.autograd.Function):
                         v(14, P2, 3) if sc_b.numel() else None,
                         v(15, P2, 4) if rot_b.numel() else None,
                         v(12, P2, 6) if cov_b.numel() else None)
+
+
+def _maps_lib():
+    """The library with the prototypes of the three map passes (hgs_maps_forward / _backward / _finish) set."""
+    lib = _load()
+    if getattr(lib, "_hgs_maps_ready", False):
+        return lib
+    lib.hgs_maps_forward.restype = C.c_int32
+    lib.hgs_maps_forward.argtypes = [C.POINTER(_ForwardArgs), C.POINTER(_ForwardState), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hgs_maps_backward.restype = C.c_int32
+    lib.hgs_maps_backward.argtypes = [C.POINTER(_BackwardArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hgs_maps_finish.restype = C.c_int32
+    lib.hgs_maps_finish.argtypes = [C.POINTER(_BackwardArgs), C.c_void_p]
+    lib._hgs_maps_ready = True
+    return lib
+
+
+class _RasterizeGaussiansMaps(torch.autograd.Function):
+    """_RasterizeGaussians with two more outputs behind its own: the accumulated-alpha map and the (un-normalised) depth map, both
+    [1,H,W], from the frame's own lists (hgs_maps_forward) -- same inputs, scratch, hints, `second` and `clamp_output` handling.
+    backward: hgs_maps_backward adds the maps' share into the accumulator, hgs_rasterize_backward turns the sum into every gradient,
+    hgs_maps_finish adds the depth's direct term to dL/dmeans3D."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, clamp_output=False, *second):
+        lib = _maps_lib()
+        out = _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                          raster_settings, clamp_output, *second)
+        dev = out[0].device
+        H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+        P = ctx.dims[0] + ctx.dims[2]
+        # P == 0: nothing is launched and the maps stay zero, as the colour does
+        new = torch.zeros if P == 0 else torch.empty
+        alpha, depth = (new(1, H, W, dtype=torch.float32, device=dev) for _ in range(2))
+        if P > 0:
+            with torch.cuda.device(dev):
+                rc = lib.hgs_maps_forward(C.byref(ctx.bw.fwd), C.byref(ctx.bw.state), alpha.data_ptr(), depth.data_ptr(),
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc < 0:
+                _raise_last(lib, "rasterize_gaussians (alpha and depth maps)")
+        return out + (alpha, depth)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, *grads):
+        lib = _maps_lib()
+        grad_alpha, grad_depth = grads[-2], grads[-1]   # (in front of them: radii's and, with_visibility, the filter's None)
+        saved = ctx.saved_tensors
+        means3D = saved[0]
+        dev = means3D.device
+        P1, M, P2, M2 = ctx.dims
+        bw, slab = ctx.bw, ctx.slab
+        with_maps = grad_alpha is not None or grad_depth is not None
+        if grad_out_color is None and not with_maps:  # no output took part in the loss
+            ctx.slab = None
+            return (None,) * (10 + ctx.n_second_inputs)
+        if slab is None:  # first use is prepared by forward; a second backward (retain_graph) gets a fresh, zeroed slab
+            slab = _grad_slab(P1, M, dev, True, bw, P2, M2)
+        ctx.slab = None
+
+        if P1 + P2 > 0:
+            H, W = int(bw.fwd.s.image_height), int(bw.fwd.s.image_width)
+            # (a missing colour gradient is a zero image: the per-Gaussian kernel runs behind the blend backward either way)
+            grad_out_color = _f32c(grad_out_color) if grad_out_color is not None else \
+                torch.zeros(3, H, W, dtype=torch.float32, device=dev)
+            grad_alpha, grad_depth = _f32c(grad_alpha), _f32c(grad_depth)
+            bw.dL_dout_color = grad_out_color.data_ptr()
+            bw.flags = HGS_BWD_UPSTREAM_SCALE_GRAD if _UPSTREAM_SCALE_GRAD else 0
+            with torch.cuda.device(dev):
+                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                if with_maps and lib.hgs_maps_backward(C.byref(bw), _ptr(grad_alpha), _ptr(grad_depth), stream) < 0:
+                    _raise_last(lib, "rasterize_gaussians_backward (alpha and depth maps)")
+                if lib.hgs_rasterize_backward(C.byref(bw), stream) < 0:
+                    _raise_last(lib, "rasterize_gaussians_backward")
+                if with_maps and lib.hgs_maps_finish(C.byref(bw), stream) < 0:
+                    _raise_last(lib, "rasterize_gaussians_backward (alpha and depth maps)")
+        return _RasterizeGaussians._input_grads(ctx, slab, saved)
 
 
 # The same binding as a C++ autograd node (ml-hugs_amd/csrc_torch/hgs_torch.cpp -> lib/_hgs_torch.so): identical library
@@ -646,8 +732,11 @@ _SECOND_KEYS = ("means3D", "shs", "colors_precomp", "opacities", "scales", "rota
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, clamp_output=False, second=None, with_visibility=False):
+                        raster_settings, clamp_output=False, second=None, with_visibility=False, return_alpha_depth=False):
     """`with_visibility`: also return `radii > 0` (bool [P]) as a third tensor, written by the kernel that writes radii.
+    `return_alpha_depth`: also return, last, the accumulated-alpha map and the un-normalised depth map sum_i w_i z_i (both [1,H,W],
+    differentiable) -- (color, radii[, visible], alpha, depth) -- from the frame's own lists; such a call goes through the ctypes
+    function _RasterizeGaussiansMaps in both binding modes.
     `second`: optional dict with the keys of _SECOND_KEYS (missing / None = absent) -- a second model's Gaussians
     rendered together with the first without concatenating anything (hgs_segment); means2D must then have
     len(means3D) + len(second["means3D"]) rows."""
@@ -656,6 +745,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     if second is not None and second.get("means3D") is not None and second["means3D"].numel():
         empty = torch.Tensor([])
         sec = tuple(second.get(k) if second.get(k) is not None else empty for k in _SECOND_KEYS)
+    if return_alpha_depth:
+        _load_cpp()   # (what this frame teaches the hint tables then reaches the C++ node's next frame of the shape: _remember)
+        return _RasterizeGaussiansMaps.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                             raster_settings, (1 if clamp_output else 0) | (2 if with_visibility else 0), *sec)
     cpp = _load_cpp()
     if cpp is not None:
         rs = raster_settings
@@ -791,8 +884,9 @@ class GaussianRasterizer(nn.Module):
         return present
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, clamp_output=False, second=None, with_visibility=False):
-        """Three additions to upstream's signature (`with_visibility`: a third return value, the bool tensor `radii > 0` that
+                cov3D_precomp=None, clamp_output=False, second=None, with_visibility=False, return_alpha_depth=False):
+        """`return_alpha_depth`: the accumulated-alpha and depth maps as two more return values, last (rasterize_gaussians).
+        Three additions to upstream's signature (`with_visibility`: a third return value, the bool tensor `radii > 0` that
         the reference's render() computes right after this call, gs_renderer.py:159, written by the kernel that writes radii): `clamp_output` -- True fuses the `torch.clamp(image, 0, 1)` that the
         reference's render() applies right after this call (gs_renderer.py:153), forward and backward -- and `second`, a
         dict (means3D, opacities, shs | colors_precomp, scales + rotations | cov3D_precomp) with a second model's Gaussians,
@@ -816,7 +910,7 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = empty
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, raster_settings, clamp_output, second, with_visibility)
+                                   cov3D_precomp, raster_settings, clamp_output, second, with_visibility, return_alpha_depth)
 
 
 # ---------------------------------------------------------------------------------------------

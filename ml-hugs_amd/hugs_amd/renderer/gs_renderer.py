@@ -91,7 +91,9 @@ def _side_stream(device):
 
 
 def render_human_scene(data, human_gs_out, scene_gs_out, bg_color, human_bg_color=None, scaling_modifier=1.0,
-                       render_mode="human_scene", render_human_separate=False):
+                       render_mode="human_scene", render_human_separate=False, return_alpha_depth=False):
+    """`return_alpha_depth` (not in the reference's signature): the main render's accumulated-alpha and depth maps as pkg["alpha"] /
+    pkg["depth"] (see render); the separate human-only render carries none."""
     g = _gather(human_gs_out, scene_gs_out, render_mode,
                 concat=not (render_mode == "human_scene" and _two_segments(human_gs_out, scene_gs_out)))
     separate = render_human_separate and render_mode == "human_scene"
@@ -106,7 +108,7 @@ def render_human_scene(data, human_gs_out, scene_gs_out, bg_color, human_bg_colo
 
     device = g["means3D"].device
     side = main = None
-    cpp = _frame_call(device) if (separate and _CONCURRENT_RENDERS and "second" in g) else None
+    cpp = _frame_call(device) if (separate and _CONCURRENT_RENDERS and "second" in g and not return_alpha_depth) else None
     if cpp is not None:
         # both renders of the step in one call, one autograd node: the human-only frame runs on a library-side stream under the joint
         # one (forward and backward) and its gradients of the human tensors are summed inside the joint frame's per-Gaussian kernel
@@ -132,7 +134,7 @@ def render_human_scene(data, human_gs_out, scene_gs_out, bg_color, human_bg_colo
                     t.record_stream(side)
     pkg = render(means3D=g["means3D"], feats=g["feats"], opacity=g["opacity"], scales=g["scales"],
                  rotations=g["rotations"], data=data, scaling_modifier=scaling_modifier, bg_color=bg_color,
-                 active_sh_degree=g["active_sh_degree"], second=g.get("second"))
+                 active_sh_degree=g["active_sh_degree"], second=g.get("second"), return_alpha_depth=return_alpha_depth)
 
     if separate:
         if human_pkg is None:
@@ -162,9 +164,12 @@ def render_human_scene(data, human_gs_out, scene_gs_out, bg_color, human_bg_colo
 
 
 def render(means3D, feats, opacity, scales, rotations, data, scaling_modifier=1.0, bg_color=None,
-           active_sh_degree=0, second=None):
+           active_sh_degree=0, second=None, return_alpha_depth=False):
     """`second` (not in the reference's signature): a dict {means3D, feats, opacity, scales, rotations} with a second model's
-    Gaussians, rendered behind the first in index order -- what the reference gets by concatenating (:33-37)."""
+    Gaussians, rendered behind the first in index order -- what the reference gets by concatenating (:33-37).
+    `return_alpha_depth` (neither): also return "alpha" and "depth", both [1,H,W] and differentiable -- the accumulated alpha
+    sum_i w_i and the un-normalised depth sum_i w_i z_i (view-space z) over the image's own contributors; the background adds
+    nothing, and depth / alpha is the caller's statement.  Such a frame takes the statement path below."""
     device = means3D.device
     if bg_color is None:
         bg_color = torch.zeros(3, dtype=torch.float32, device=device)
@@ -175,7 +180,7 @@ def render(means3D, feats, opacity, scales, rotations, data, scaling_modifier=1.
     # `.grad` receives the rasterizer's gradient buffer itself (no clone), the values are the same zeros, and everything the
     # trainer does with it (reads .grad, slices it, re-assigns it: gs_trainer.py:316-342) works alike.
     # HGS_VIEWSPACE_NONLEAF=1 restores the reference's construction.
-    cpp = _frame_call(device)
+    cpp = None if return_alpha_depth else _frame_call(device)
     if cpp is not None:
         sec = [] if second is None else [second["means3D"], second["feats"], second["opacity"], second["scales"], second["rotations"]]
         image, radii, visible, screenspace_points = cpp.render(
@@ -223,14 +228,18 @@ def render(means3D, feats, opacity, scales, rotations, data, scaling_modifier=1.
         clamp_output=True,   # the reference's torch.clamp(rendered_image, 0.0, 1.0) (:153), fused into the blend kernels
         **({} if second is None else {"second": second}),   # (a one-model call carries exactly the reference's kwargs + the clamp)
         **({"with_visibility": True} if _FUSED_VISIBILITY else {}),
+        **({"return_alpha_depth": True} if return_alpha_depth else {}),
     )
     image, radii = out[0], out[1]
-    return {
+    pkg = {
         "render": image,
         "viewspace_points": screenspace_points,
-        "visibility_filter": out[2] if len(out) > 2 else radii > 0,
+        "visibility_filter": out[2] if len(out) > (4 if return_alpha_depth else 2) else radii > 0,
         "radii": radii,
     }
+    if return_alpha_depth:
+        pkg["alpha"], pkg["depth"] = out[-2], out[-1]
+    return pkg
 
 
 # ---------------------------------------------------------------------------------------------

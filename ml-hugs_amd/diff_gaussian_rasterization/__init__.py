@@ -285,7 +285,7 @@ def _ckpt_hint(key):
 _HINT_SHAPES = 256   # shapes remembered (densification changes P all the time: do not grow without bound)
 
 
-def _remember(key, n, has_long, sparse=None, to_cpp=True):
+def _remember(key, n, has_long, sparse=None, to_cpp=True, ckpt_used=None):
     # least recently used shapes go first -- not the whole table at once (round 3 wiped all three tables at 256 shapes: a
     # densifying run then paid one blocking frame per live shape each time); dicts keep insertion order, re-inserting = touching
     _last_num_rendered.pop(key, None)
@@ -297,8 +297,11 @@ def _remember(key, n, has_long, sparse=None, to_cpp=True):
         _last_ckpt_used.pop(old, None)
     if sparse is not None:
         _last_sparse[key] = bool(sparse)
-    if to_cpp and _cpp is not None:   # ... and what the Python paths learnt, the C++ node uses
-        _cpp.set_hint(key[0], key[1], key[2], key[3], n, has_long, _last_sparse.get(key, True))
+    if ckpt_used is not None:   # (a frame that says nothing about checkpoints -- a deferred one -- leaves the shape's count as it is)
+        _last_ckpt_used[key] = int(ckpt_used)
+    if to_cpp and _cpp is not None:   # ... and what the Python paths learnt, the C++ node uses -- the checkpoint-slot count included:
+        # without it the node's next frame of the shape asks for the full layout again, or for checkpoints a frame said it leaves none of
+        _cpp.set_hint(key[0], key[1], key[2], key[3], n, has_long, _last_sparse.get(key, True), _last_ckpt_used.get(key, 0))
     _last_num_rendered[key] = (n, has_long)
     _max_num_rendered[key] = max(n, _max_num_rendered.get(key, 0))
 
@@ -532,8 +535,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = int(n)
         ctx.binning_capacity = int(state.binning_capacity)
         _last_frame_info = (ctx.num_rendered, ctx.binning_capacity)
-        _remember(hint_key, int(n), bool(state.has_long_tiles), bool(state.sparse_frame))
-        _last_ckpt_used[hint_key] = int(state.ckpt_slots_used)
+        _remember(hint_key, int(n), bool(state.has_long_tiles), bool(state.sparse_frame), ckpt_used=int(state.ckpt_slots_used))
         ctx.bw, ctx.slab, ctx.keep, ctx.dims = bw, slab, keep, (P1, M, P2, M2)
         ctx.scratch, ctx.bufs = scratch, bufs   # kept alive for backward (and read by _debug_forward_state)
         empty = torch.empty(0, device=dev)
@@ -760,7 +762,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         n, cap, has_long, sparse = cpp.last_frame_info()
         _last_frame_info = (n, cap)
         if radii.numel():   # one hint table for both bindings: what the C++ node learnt, the Python paths (deferred frames) use
-            _remember((means3D.device.index, radii.numel(), int(rs.image_height), int(rs.image_width)), n, has_long, sparse, to_cpp=False)
+            _remember((means3D.device.index, radii.numel(), int(rs.image_height), int(rs.image_width)), n, has_long, sparse, to_cpp=False,
+                      ckpt_used=cpp.last_ckpt_info()[1])
         return (color, radii, visible) if with_visibility else (color, radii)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, (1 if clamp_output else 0) | (2 if with_visibility else 0), *sec)

@@ -20,6 +20,15 @@ def map_upstreams(H, W, seed=77):
     return rng.standard_normal((H, W)).astype(np.float32), rng.standard_normal((H, W)).astype(np.float32)
 
 
+def smooth_map_upstreams(H, W):
+    """(gA, gD): two low-frequency sinusoids in pixel coordinates, values in 0.1 .. 1.0, of different phase, [H, W] float32 each.
+    Under the noise of map_upstreams a gradient's sum can nearly cancel, and the few pixels that take the other side of a threshold
+    in another precision then weigh in at 1e-3 of it (tests/test_gpu_maps_paths.py measures both); under these it does not."""
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    wave = lambda fx, fy, phase: 0.55 + 0.45 * np.sin(2.0 * np.pi * (fx * x / W + fy * y / H) + phase)
+    return wave(1.5, 1.0, 0.3).astype(np.float32), wave(1.0, 2.0, 1.9).astype(np.float32)
+
+
 def maps_reference(sc, gA=None, gD=None, dtype=np.float32):
     """The oracle's maps of scene `sc` (tests/scenes.make_scene) and, given upstream gradients, their gradients.
     Returns dict(alpha [H,W], depth [H,W], z [P], z_max, fwd (the oracle's forward of the (z, 1, 0) render), grads or None)."""

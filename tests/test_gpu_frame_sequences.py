@@ -290,8 +290,10 @@ class _Scene:
         self.t = {k: to_dev(base[k], device) for k in ("means3D", "opacities", "shs", "scales", "rotations")}
         self.dL = to_dev(base["dL_dpix"], device)
 
-    def render(self, fr, lib, cpp, backward=True):
-        """one frame through GaussianRasterizer [+ backward]: (record of what ran, image, radii, {gradients})"""
+    def render(self, fr, lib, cpp, backward=True, maps=None):
+        """one frame through GaussianRasterizer [+ backward]: (record of what ran, image, radii, {gradients})
+        maps=(gA, gD), device tensors [H, W]: the call has return_alpha_depth=True -- it then goes through the ctypes function whatever
+        the binding --, the loss gains (alpha * gA).sum() + (depth * gD).sum(), and the record the two maps (tests/test_gpu_maps_paths.py)"""
         from diff_gaussian_rasterization import GaussianRasterizer
         stat = lambda k: lib.hgs_debug_stat(k.encode())
         before = stat("binning_reruns"), stat("ckpt_reruns")
@@ -299,16 +301,20 @@ class _Scene:
         leaves = {k: v.detach().clone().requires_grad_(True) for k, v in self.t.items()}
         means2D = torch.zeros(P, 3, device=self.device, requires_grad=True)
         rast = GaussianRasterizer(gpu_settings(fr, self.device))
+        flag = dict(return_alpha_depth=True) if maps is not None else {}
         if self.cut is None:
-            color, radii = rast(means3D=leaves["means3D"], means2D=means2D, opacities=leaves["opacities"], shs=leaves["shs"],
-                                scales=leaves["scales"], rotations=leaves["rotations"])
+            color, radii, *ad = rast(means3D=leaves["means3D"], means2D=means2D, opacities=leaves["opacities"], shs=leaves["shs"],
+                                     scales=leaves["scales"], rotations=leaves["rotations"], **flag)
         else:   # the rows from `cut` on first, the rows before it as the second set (hgs_segment): the caller's frame has them in that order
             a = {k: v.detach()[self.cut:].clone().requires_grad_(True) for k, v in self.t.items()}
             b = {k: v.detach()[:self.cut].clone().requires_grad_(True) for k, v in self.t.items()}
-            color, radii = rast(means3D=a["means3D"], means2D=means2D, opacities=a["opacities"], shs=a["shs"], scales=a["scales"],
-                                rotations=a["rotations"], second=b)
+            color, radii, *ad = rast(means3D=a["means3D"], means2D=means2D, opacities=a["opacities"], shs=a["shs"], scales=a["scales"],
+                                     rotations=a["rotations"], second=b, **flag)
+        assert len(ad) == (2 if maps is not None else 0)
         rec = dict(fwd_forms=int(stat("last_forward_forms")))
-        if cpp is not None:
+        if maps is not None:
+            rec["alpha"], rec["depth"] = ad[0].detach(), ad[1].detach()
+        if cpp is not None and maps is None:
             assert color.grad_fn is None or color.grad_fn.name() == "HgsRasterizeBackward"
             rec["N"], rec["capacity"], rec["has_long"], rec["sparse"] = cpp.last_frame_info()
             rec["ckpt_bytes"], rec["ckpt_used"] = cpp.last_ckpt_info()
@@ -319,7 +325,10 @@ class _Scene:
                        ckpt_bytes=int(s.ckpt_bytes), ckpt_used=int(s.ckpt_slots_used))
         grads = {}
         if backward:
-            color.backward(self.dL)
+            if maps is None:
+                color.backward(self.dL)
+            else:
+                ((color * self.dL).sum() + (ad[0][0] * maps[0]).sum() + (ad[1][0] * maps[1]).sum()).backward()
             torch.cuda.synchronize()
             rec["bwd_forms"] = int(stat("last_backward_forms"))
             if self.cut is None:

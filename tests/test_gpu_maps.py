@@ -50,9 +50,11 @@ def reference(name):
     return sc, gA, gD, maps_reference(sc, gA, gD), f, g
 
 
-def rasterize(sc, device, **extra):
+def rasterize(sc, device, grad=True, **extra):
     from diff_gaussian_rasterization import GaussianRasterizer
-    t = gpu_tensors(sc, device)
+    t = gpu_tensors(sc, device, grad)
+    if not grad:
+        t["means2D"] = t["means2D"].detach()
     out = GaussianRasterizer(gpu_settings(sc, device))(
         means3D=t["means3D"], means2D=t["means2D"], opacities=t["opacities"], shs=t["shs"], colors_precomp=t["colors_precomp"],
         scales=t["scales"], rotations=t["rotations"], cov3D_precomp=t["cov3D_precomp"], **extra)
@@ -73,8 +75,8 @@ def check_maps(alpha, depth, ref, what):
     check_image(d / ref["z_max"], ref["depth"] / ref["z_max"], f"{what} depth / z_max")
 
 
-def check_grads(got, want, sc, what, tol=GRAD_REL_TOL):
-    for k, rk in GRAD_KEYS:
+def check_grads(got, want, sc, what, tol=GRAD_REL_TOL, keys=GRAD_KEYS):
+    for k, rk in keys:
         if sc.get(k) is None and k != "means2D":
             continue
         assert k in got, f"{what}: no gradient for {k}"
@@ -268,6 +270,93 @@ def test_both_bindings_give_the_same_maps(device, monkeypatch):
         assert torch.equal(x, y)
 
 
+GEOMETRY_GRAD_KEYS = tuple((k, rk) for k, rk in GRAD_KEYS if k not in ("shs", "colors_precomp"))
+
+
+@functools.lru_cache(maxsize=None)
+def normalised_depth_reference(name):
+    """The oracle's gradients of (depth / alpha.clamp_min(1e-6)).sum(): the chain rule in fp64 on the oracle's own maps -- gD = 1 /
+    max(alpha, 1e-6), gA = -depth / alpha^2 where alpha exceeds 1e-6 (the clamp passes no gradient below), else 0 -- and the oracle's
+    backward under these upstreams.  (A pixel with a contributor has alpha >= 1/255: the upstreams stay below 255 and 255^2 z_max.)"""
+    sc, _, _, ref, _, _ = reference(name)
+    a, d = ref["alpha"].astype(np.float64), ref["depth"].astype(np.float64)
+    live = a > 1e-6
+    gD = 1.0 / np.maximum(a, 1e-6)
+    gA = np.where(live, -d / np.where(live, a, 1.0) ** 2, 0.0)
+    return maps_reference(sc, gA, gD)["grads"]
+
+
+@pytest.mark.parametrize("name", ["basic_d3", "deep_stop"])
+def test_the_callers_normalisation_against_the_oracle(name, device):
+    """(depth / alpha.clamp_min(1e-6)).sum(), the expected depth a caller forms from the two maps: upstream gradients that depend on
+    the maps themselves, every geometry gradient against the oracle's."""
+    sc = scene_of(name)
+    t, (_, _, alpha, depth) = rasterize(sc, device, return_alpha_depth=True)
+    (depth / alpha.clamp_min(1e-6)).sum().backward()
+    torch.cuda.synchronize()
+    check_grads(grads_of(t), normalised_depth_reference(name), sc, f"{name}, depth / alpha", keys=GEOMETRY_GRAD_KEYS)
+    for k in ("shs", "colors_precomp"):
+        if t[k] is not None:
+            assert float(t[k].grad.abs().max()) == 0.0, k
+
+
+def test_visibility_filter_together_with_the_maps(device):
+    """with_visibility=True and return_alpha_depth=True in one call: (colour, radii, filter, alpha, depth) -- backward finds the maps'
+    gradients behind radii's AND the filter's None."""
+    sc, gA, gD, ref, _, _ = reference("basic_d3")
+    tA, tD, dL = to_dev(gA, device), to_dev(gD, device), to_dev(sc["dL_dpix"], device)
+    grads = []
+    for extra in (dict(), dict(with_visibility=True)):
+        t, out = rasterize(sc, device, return_alpha_depth=True, **extra)
+        assert len(out) == 4 + len(extra)
+        color, radii, alpha, depth = out[0], out[1], out[-2], out[-1]
+        ((color * dL).sum() + (alpha[0] * tA).sum() + (depth[0] * tD).sum()).backward()
+        torch.cuda.synchronize()
+        grads.append((out, grads_of(t)))
+    (plain, g0), (five, g1) = grads
+    color, radii, visible, alpha, depth = five
+    assert visible.dtype == torch.bool and visible.shape == radii.shape and torch.equal(visible, radii > 0) and bool(visible.any())
+    assert not visible.requires_grad and not radii.requires_grad and alpha.requires_grad and depth.requires_grad
+    assert alpha.shape == (1, sc["H"], sc["W"]) and depth.shape == alpha.shape and color.shape == (3, sc["H"], sc["W"])
+    for a, b in zip((color, radii, alpha, depth), plain):
+        assert torch.equal(a, b)
+    check_maps(alpha, depth, ref, "with the visibility filter")
+    assert set(g0) == set(g1)
+    for k in g0:
+        err = rel_l2(g1[k], g0[k])
+        print(f"with the visibility filter: grad {k} against the call without it {err:.2e}")
+        assert err <= order_tol(k), (k, err)
+
+
+def test_maps_without_a_graph_come_from_the_streams_arena(device):
+    """Under torch.no_grad() and with inputs that ask for no gradient the frame's scratch is the stream's arena, which the next frame
+    on the stream overwrites: the maps are bit-equal to the grad-enabled call's, and -- cloned before it -- still are after another
+    frame has used the arena.  (Inputs that require a gradient keep the frame on scratch of its own under no_grad as well:
+    ctx.needs_input_grad does not look at the grad mode; that call is held to the same.)"""
+    import diff_gaussian_rasterization as dgr
+    first, second = scene_of("basic_d3"), scene_of("rotcam_d2")
+    assert (first["H"], first["W"], first["means3D"].shape[0]) != (second["H"], second["W"], second["means3D"].shape[0])
+    want = {}
+    for name, sc in (("first", first), ("second", second)):
+        _, (color, radii, alpha, depth) = rasterize(sc, device, return_alpha_depth=True)
+        assert alpha.grad_fn is not None
+        want[name] = (color.detach().clone(), alpha.detach().clone(), depth.detach().clone())
+    for grad in (False, True):
+        with torch.no_grad():
+            dgr._arenas.clear()
+            _, (color, radii, alpha, depth) = rasterize(first, device, grad=grad, return_alpha_depth=True)
+            assert alpha.grad_fn is None and not alpha.requires_grad
+            assert len(dgr._arenas) == (0 if grad else 1), "the frame's scratch is not where this test says it is"
+            kept = (color.clone(), alpha.clone(), depth.clone())
+            _, (color2, _, alpha2, depth2) = rasterize(second, device, grad=grad, return_alpha_depth=True)
+            torch.cuda.synchronize()
+            assert len(dgr._arenas) == (0 if grad else 1)
+        for what, got, ref in (("first", kept, want["first"]), ("second", (color2, alpha2, depth2), want["second"])):
+            for k, a, b in zip(("colour", "alpha", "depth"), got, ref):
+                assert torch.equal(a, b), f"{what}, inputs require grad: {grad}: {k} differs from the grad-enabled call's on {int((a != b).sum())} pixels"
+    check_maps(kept[1], kept[2], reference("basic_d3")[3], "no_grad")
+
+
 def test_render_returns_the_two_maps(device):
     from hugs_amd.renderer import gs_renderer
     from test_gpu_configs import cam_data
@@ -283,7 +372,10 @@ def test_render_returns_the_two_maps(device):
     assert torch.equal(pkg["visibility_filter"], pkg["radii"] > 0)
     check_maps(pkg["alpha"], pkg["depth"], ref, "render()")
     (pkg["depth"] / pkg["alpha"].clamp_min(1e-6)).sum().backward()   # the caller's normalisation
-    assert torch.isfinite(t["means3D"].grad).all() and float(pkg["viewspace_points"].grad.abs().max()) > 0.0
+    torch.cuda.synchronize()
+    assert float(pkg["viewspace_points"].grad.abs().max()) > 0.0
+    got = dict(grads_of(t), means2D=pkg["viewspace_points"].grad.detach().cpu().numpy())
+    check_grads(got, normalised_depth_reference("basic_d3"), sc, "render(), depth / alpha", keys=GEOMETRY_GRAD_KEYS)
 
 
 def test_render_human_scene_returns_the_main_renders_maps(device):

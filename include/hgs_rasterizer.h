@@ -469,6 +469,39 @@ int32_t hgs_mlp_backward(int32_t n, const hgs_mlp_desc *net, const float *x, con
 /* Points per tile of the two kernels (a launch-shape fact for tests that want sizes around it; results do not depend on it). */
 int32_t hgs_mlp_tile(void);
 
+/* Row f-10 -- the SMPL body model's forward from (betas, pose, transl) to vertices and joint transforms, fused: replaces
+ * SMPL.forward (/root/reference/hugs/models/modules/smpl_layer.py:411-519, called every human step at
+ * /root/reference/hugs/models/hugs_trimlp.py:458) and the lbs() it calls (/root/reference/hugs/models/modules/lbs.py:76-187), for
+ * one batch element, fp32:
+ *   shape_offsets[v,k] = sum_l shapedirs[v,k,l] betas[l]   v_shaped = v_template + shape_offsets   Jrest = J_regressor v_shaped
+ *   R_j = I + sin a K + (1 - cos a) K^2, a = |pose_j + 1e-8|, K = hat(pose_j / a)      (Rodrigues, epsilon inside the norm)
+ *   pose_offsets = flatten(R[1:] - I) posedirs ([P] x [P,3V], P = 9 (J - 1))          v_posed = v_shaped + pose_offsets
+ *   G_0 = [R_0 | Jrest_0], G_j = G_parents[j] [R_j | Jrest_j - Jrest_parents[j]]     J_transformed_j = G_j[:3,3] + transl
+ *   A_j = G_j with translation t_j - G_j[:3,:3] Jrest_j (+ transl)     T_v = sum_j lbs_weights[v,j] A_j (without transl; + transl)
+ *   verts_v = T_v [v_posed_v, 1] (+ transl)
+ * V >= 0 vertices (V == 0: nothing is launched or written, returns 0), 2 <= J <= 32 joints, 1 <= NB <= 16 shape coefficients.
+ * `parents` is a HOST array [J] with parents[0] = -1 and 0 <= parents[j] < j.  betas [NB], pose [3J] axis-angle, transl [3] or NULL,
+ * v_template [V,3], shapedirs [V,3,NB], posedirs [P,3V] (NULL is legal with disable_posedirs: it is not read, pose_offsets = 0),
+ * J_regressor [J,V], lbs_weights [V,J].  Outputs: verts [V,3], J_transformed [J,3], A [J,16], T [V,16], v_posed, v_shaped,
+ * shape_offsets, pose_offsets [V,3]; T and workspace 16-byte aligned.  `workspace`: hgs_smpl_workspace(V, J, NB) bytes (0 for
+ * V == 0, monotone in V); the forward leaves R, Jrest, G and the pose feature at its head, so the backward of a forward must be
+ * given the same, untouched workspace.  Bad sizes, a bad `parents` or a null required pointer return < 0 before any launch. */
+size_t hgs_smpl_workspace(int32_t V, int32_t J, int32_t NB);
+int32_t hgs_smpl_forward(int32_t V, int32_t J, int32_t NB, const int32_t *parents, const float *betas, const float *pose,
+                         const float *transl, const float *v_template, const float *shapedirs, const float *posedirs,
+                         const float *J_regressor, const float *lbs_weights, int32_t disable_posedirs, float *verts,
+                         float *J_transformed, float *A, float *T, float *v_posed, float *v_shaped, float *shape_offsets,
+                         float *pose_offsets, void *workspace, void *stream);
+/* Its backward (autograd's pass over the same statements): dL_dbetas [NB], dL_dpose [3J] and dL_dtransl [3] (may be NULL) given the
+ * gradients of the eight outputs, each of which may be NULL (= zero, costs nothing).  v_posed and T are the forward's outputs.  The
+ * model buffers get no gradient.  Every sum is per-workgroup partials finished in a fixed order: no float atomics, bit-reproducible. */
+int32_t hgs_smpl_backward(int32_t V, int32_t J, int32_t NB, const int32_t *parents, const float *pose, const float *shapedirs,
+                          const float *posedirs, const float *J_regressor, const float *lbs_weights, int32_t disable_posedirs,
+                          const float *v_posed, const float *T, const float *dL_dverts, const float *dL_dJ_transformed,
+                          const float *dL_dA, const float *dL_dT, const float *dL_dv_posed, const float *dL_dv_shaped,
+                          const float *dL_dshape_offsets, const float *dL_dpose_offsets, float *dL_dbetas, float *dL_dpose,
+                          float *dL_dtransl, void *workspace, void *stream);
+
 /* Message for the last negative return value on the calling thread. */
 const char *hgs_last_error(void);
 

@@ -502,6 +502,35 @@ int32_t hgs_smpl_backward(int32_t V, int32_t J, int32_t NB, const int32_t *paren
                           const float *dL_dshape_offsets, const float *dL_dpose_offsets, float *dL_dbetas, float *dL_dpose,
                           float *dL_dtransl, void *workspace, void *stream);
 
+/* SURVEY.md 8f row f-11 -- the Adam step of the two models' optimizers, many tensors per launch: replaces the
+ * `self.optimizer.step()` calls of the trainer (/root/reference/hugs/trainer/gs_trainer.py:344-351) on the optimizers built as
+ * torch.optim.Adam(params, lr=0.0, eps=1e-15) at /root/reference/hugs/models/scene.py:213 and
+ * /root/reference/hugs/models/hugs_trimlp.py:701, one parameter group per tensor.  fp32, in place, per tensor i and element:
+ *   m' = m + (g - m) * one_minus_beta1          v' = v * beta2 + one_minus_beta2 * g * g
+ *   p' = p - step_size * (m' / (sqrt(v') / bc2_sqrt + eps))
+ * exactly as spelled (no contraction, correctly rounded divide and sqrt): the single-tensor, non-capturable form of
+ * torch.optim.Adam without weight decay / amsgrad / maximize.  The caller forms step_size = lr / (1 - beta1^t) and
+ * bc2_sqrt = sqrt(1 - beta2^t) in double from the tensor's own step count t (after its increment) and rounds once.
+ * Every tensor is `numel` consecutive floats behind each of its four pointers (4-byte alignment suffices; a tensor whose four
+ * pointers are 16-byte aligned moves as 16-byte vectors).  Tensors must not overlap one another.  A record with numel == 0 is
+ * skipped (its pointers are not looked at).  The records travel by value in the kernel argument, hgs_adam_limits()'s
+ * tensors_per_launch of them per launch, one workgroup per chunk_elems elements of a tensor: no device allocation, no copy, no
+ * host synchronisation; n records are ceil(non-empty / tensors_per_launch) launches of one kernel.  Everything is validated
+ * before the first launch: n < 0, a null `tensors`, and per record numel < 0, a null or not 4-byte-aligned pointer, a
+ * non-finite scalar or bc2_sqrt <= 0 return HGS_ERR_INVALID_ARGUMENT and nothing is launched.  n == 0 returns 0. */
+typedef struct hgs_adam_tensor {
+    float *param;            /* [numel] updated in place */
+    const float *grad;       /* [numel] */
+    float *exp_avg;          /* [numel] m, updated in place */
+    float *exp_avg_sq;       /* [numel] v, updated in place */
+    int64_t numel;
+    float one_minus_beta1, beta2, one_minus_beta2, eps;
+    float step_size, bc2_sqrt;
+} hgs_adam_tensor;           /* 64 bytes */
+int32_t hgs_adam_step(const hgs_adam_tensor *tensors, int32_t n, void *stream);
+/* Launch-shape facts for tests and wrappers (results do not depend on them): records per launch, elements per workgroup. */
+void hgs_adam_limits(int32_t *tensors_per_launch, int32_t *chunk_elems);
+
 /* Message for the last negative return value on the calling thread. */
 const char *hgs_last_error(void);
 

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 11
+#define HGS_ABI_VERSION 12
 
 /* scratch buffer ids passed to the allocation callback */
 enum { HGS_BUF_GEOM = 0, HGS_BUF_BINNING = 1, HGS_BUF_IMAGE = 2, HGS_BUF_CKPT = 3, HGS_NUM_BUFS = 4 };
@@ -382,6 +382,31 @@ int32_t hgs_ssim_l1_forward(int32_t C, int32_t H, int32_t W, const float *img1, 
  * SSIM term. */
 int32_t hgs_ssim_l1_backward(int32_t C, int32_t H, int32_t W, const float *img1, const float *img2, const float *maps,
                              const float *g_ssim_mean, const float *g_l1_sum, float *dL_dimg1, void *stream);
+
+/* Row f-5 with the masks of HumanSceneLoss.forward (hugs/losses/loss.py:46-162): the same two terms on the composites the
+ * reference builds from the render `pred` [C,H,W], the target `gt` [C,H,W], the human mask `mask` [H,W] and one background colour
+ * per channel `bg` [C] (device pointers, fp32, contiguous; bg may be NULL in the scene mode).  The composites are formed while the
+ * tiles are loaded, none is written to memory:
+ *   HGS_MASKED_HUMAN: x = pred,               y = gt * mask + bg[c] * (1 - mask)
+ *   HGS_MASKED_SCENE: x = pred * (1 - mask),  y = gt * (1 - mask)
+ *   out[0] = sum |x - y| / sum(mask)                                    (the reference's Ll1)
+ *   out[1] = (1 - mean of the SSIM map of x, y) * sum(mask) / (H * W)   (the reference's loss_ssim)
+ *   out[2] = sum(mask), out[3] = mean of the SSIM map
+ * BOTH modes divide by and scale with the sum of `mask` itself, as the reference does (its scene mode inverts the mask twice).
+ * sum(mask) = 0 is an IEEE division on the device (inf or nan in out[0]); nothing is reported.  maps: [3,C,H,W] floats kept for the
+ * backward, or NULL for a forward-only evaluation.  workspace: hgs_masked_loss_workspace(C,H,W) bytes, 16-byte aligned (per-workgroup
+ * partial sums; the totals are formed in a fixed order in double: bit-reproducible).  The images and the mask move as float4 when W
+ * is a multiple of 4 and all of them are 16-byte aligned, element by element otherwise, with the same values. */
+enum { HGS_MASKED_HUMAN = 1, HGS_MASKED_SCENE = 2 };
+size_t hgs_masked_loss_workspace(int32_t C, int32_t H, int32_t W);
+int32_t hgs_masked_loss_forward(int32_t mode, int32_t C, int32_t H, int32_t W, const float *pred, const float *gt,
+                                const float *mask, const float *bg, float *maps, void *workspace, float *out, void *stream);
+/* dL/dpred [C,H,W] = g_l1[0] * d(out[0])/dpred + g_ssim_term[0] * d(out[1])/dpred.  Both factors are DEVICE scalars (the autograd
+ * gradients of the two terms), either may be NULL (= 0); terms: forward's out (its sum(mask) is read on the device: no host round
+ * trip).  maps: forward's, needed when g_ssim_term is given.  pred is the only differentiable input. */
+int32_t hgs_masked_loss_backward(int32_t mode, int32_t C, int32_t H, int32_t W, const float *pred, const float *gt,
+                                 const float *mask, const float *bg, const float *maps, const float *terms, const float *g_l1,
+                                 const float *g_ssim_term, float *dL_dpred, void *stream);
 
 /* Row f-6 -- the statements that produce the rasterizer's inputs on every training step, fused: replaces SceneGS.forward
  * (/root/reference/hugs/models/scene.py:147-160): scales = exp(scaling) [P,3], rotq = normalize(rotation) [P,4] (x / max(|x|,

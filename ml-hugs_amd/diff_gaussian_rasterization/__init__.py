@@ -25,6 +25,8 @@ from typing import NamedTuple
 import torch
 import torch.nn as nn
 
+from ._abi import _ALLOC_FN, _BackwardArgs, _ForwardArgs, _ForwardState, _Segment, _Settings, bind  # noqa: F401 (the struct names are part of what this package exports)
+
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_deferred", "DeferredFrame",
            "library_path", "set_upstream_scale_grad"]
 
@@ -39,51 +41,7 @@ def library_path():
 
 
 # ---------------------------------------------------------------------------------------------
-# ctypes mirror of include/hgs_rasterizer.h
-class _Settings(C.Structure):
-    _fields_ = [("image_height", C.c_int32), ("image_width", C.c_int32), ("tanfovx", C.c_float),
-                ("tanfovy", C.c_float), ("bg", C.c_void_p), ("scale_modifier", C.c_float),
-                ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p), ("sh_degree", C.c_int32),
-                ("campos", C.c_void_p), ("prefiltered", C.c_int32), ("debug", C.c_int32)]
-
-
-class _Segment(C.Structure):
-    _fields_ = [("P", C.c_int32), ("M", C.c_int32), ("means3D", C.c_void_p), ("shs", C.c_void_p), ("colors_precomp", C.c_void_p),
-                ("opacities", C.c_void_p), ("scales", C.c_void_p), ("rotations", C.c_void_p), ("cov3D_precomp", C.c_void_p)]
-
-
-class _ForwardArgs(C.Structure):
-    _fields_ = [("s", _Settings), ("P", C.c_int32), ("M", C.c_int32), ("means3D", C.c_void_p),
-                ("shs", C.c_void_p), ("colors_precomp", C.c_void_p), ("opacities", C.c_void_p),
-                ("scales", C.c_void_p), ("rotations", C.c_void_p), ("cov3D_precomp", C.c_void_p),
-                ("out_color", C.c_void_p), ("radii", C.c_void_p), ("binning_capacity_hint", C.c_int64),
-                ("grad_accum_to_zero", C.c_void_p), ("clamp_output", C.c_int32), ("expect_no_long_tiles", C.c_int32),
-                ("defer_n", C.c_int32), ("backward_checkpoints", C.c_int32), ("scratch", C.c_void_p * 4),
-                ("scratch_bytes", C.c_size_t * 4), ("seg2", _Segment), ("visible", C.c_void_p), ("ckpt_slots_hint", C.c_int64),
-                ("before_wait", C.c_void_p), ("before_wait_ctx", C.c_void_p)]
-
-
-class _ForwardState(C.Structure):
-    _fields_ = [("geom", C.c_void_p), ("geom_bytes", C.c_size_t), ("binning", C.c_void_p),
-                ("binning_bytes", C.c_size_t), ("image", C.c_void_p), ("image_bytes", C.c_size_t),
-                ("ckpt", C.c_void_p), ("ckpt_bytes", C.c_size_t), ("num_rendered", C.c_int64), ("binning_capacity", C.c_int64), ("sparse_frame", C.c_int32),
-                ("has_long_tiles", C.c_int32), ("n_token", C.c_uint64), ("ckpt_slots", C.c_int64), ("ckpt_slots_used", C.c_int64)]
-
-
-class _BackwardArgs(C.Structure):
-    _fields_ = [("fwd", _ForwardArgs), ("state", _ForwardState), ("dL_dout_color", C.c_void_p),
-                ("grad_accum", C.c_void_p), ("dL_dmeans2D", C.c_void_p), ("dL_dopacity", C.c_void_p),
-                ("dL_dcolors", C.c_void_p), ("dL_dmeans3D", C.c_void_p), ("dL_dcov3D", C.c_void_p),
-                ("dL_dsh", C.c_void_p), ("dL_dscales", C.c_void_p), ("dL_drotations", C.c_void_p),
-                ("seg2_dL_dopacity", C.c_void_p), ("seg2_dL_dcolors", C.c_void_p), ("seg2_dL_dmeans3D", C.c_void_p),
-                ("seg2_dL_dcov3D", C.c_void_p), ("seg2_dL_dsh", C.c_void_p), ("seg2_dL_dscales", C.c_void_p),
-                ("seg2_dL_drotations", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32),
-                ("add_dL_dopacity", C.c_void_p), ("add_dL_dcolors", C.c_void_p), ("add_dL_dmeans3D", C.c_void_p),
-                ("add_dL_dcov3D", C.c_void_p), ("add_dL_dsh", C.c_void_p), ("add_dL_dscales", C.c_void_p),
-                ("add_dL_drotations", C.c_void_p), ("wait_before_per_gaussian", C.c_void_p)]
-
-
-_ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)
+# the ctypes mirror of include/hgs_rasterizer.h -- structs, prototypes, bind() -- is _abi.py
 HGS_BWD_UPSTREAM_SCALE_GRAD = 1
 # dL/dscales: the true derivative (includes settings.scale_modifier) by default; True reproduces the published kernel, which
 # omits the factor (both bindings; HGS_UPSTREAM_SCALE_GRAD=1 in the environment, or set_upstream_scale_grad()).  The two
@@ -109,42 +67,9 @@ def _load():
             f"diff_gaussian_rasterization (MI355X): {_LIB_PATH} not found. Build it with "
             "`make -C ml-hugs_amd/csrc` (or __graft_entry__.build()). There is no CPU fallback.")
     lib = C.CDLL(_LIB_PATH)
-    lib.hgs_abi_version.restype = C.c_int32
     if lib.hgs_abi_version() != _ABI_VERSION:
         raise RuntimeError("libhgs_rasterizer.so ABI version mismatch; rebuild it")
-    lib.hgs_rasterize_forward.restype = C.c_int64
-    lib.hgs_rasterize_forward.argtypes = [C.POINTER(_ForwardArgs), _ALLOC_FN, C.c_void_p,
-                                          C.POINTER(_ForwardState), C.c_void_p]
-    lib.hgs_rasterize_backward.restype = C.c_int32
-    lib.hgs_rasterize_backward.argtypes = [C.POINTER(_BackwardArgs), C.c_void_p]
-    lib.hgs_forward_poll.restype = C.c_int64
-    lib.hgs_forward_poll.argtypes = [C.POINTER(_ForwardState), C.c_int32, C.c_void_p]
-    lib.hgs_mark_visible.restype = C.c_int32
-    lib.hgs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.hgs_last_error.restype = C.c_char_p
-    for fn in (lib.hgs_geom_bytes, lib.hgs_image_bytes, lib.hgs_binning_bytes, lib.hgs_ckpt_bytes, lib.hgs_ckpt_bytes_for_slots, lib.hgs_scratch_offset):
-        fn.restype = C.c_size_t
-    lib.hgs_ckpt_bytes_for_slots.argtypes = [C.c_int64]
-    lib.hgs_ckpt_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    lib.hgs_geom_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.hgs_image_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.hgs_binning_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    lib.hgs_scratch_offset.argtypes = [C.c_char_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
-    lib.hgs_debug_stat.argtypes = [C.c_char_p]
-    lib.hgs_debug_stat.restype = C.c_int64
-    lib.hgs_reload_switches.argtypes = []
-    lib.hgs_reload_switches.restype = None
-    lib.hgs_copy_bandwidth.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.hgs_copy_bandwidth.restype = C.c_int32
-    lib.hgs_profile_enable.argtypes = [C.c_uint32]
-    lib.hgs_profile_enable.restype = None
-    lib.hgs_profile_reset.restype = None
-    lib.hgs_profile_set_sampling.argtypes = [C.c_uint32]
-    lib.hgs_profile_set_sampling.restype = None
-    lib.hgs_profile_read.argtypes = [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.hgs_profile_read.restype = C.c_int32
-    lib.hgs_stage_name.argtypes = [C.c_int32]
-    lib.hgs_stage_name.restype = C.c_char_p
+    bind(lib)   # every prototype, once: no other code sets one
     _lib = lib
     return lib
 
@@ -209,8 +134,28 @@ def _aligned(t):
     return t.clone() if t.data_ptr() % 16 else t
 
 
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def _launch(dev, what, fn, *args):
+    """One library call of a row on the device the caller has made current: fn(*args, torch's current stream on `dev`); a negative
+    return raises hgs_last_error() under the name `what`."""
+    if fn(*args, torch.cuda.current_stream(dev).cuda_stream) < 0:
+        _raise_last(_lib, what)
+
+
+def _call(dev, what, fn, *args):
+    """_launch with `dev` made current around it (a loop over batch elements holds one guard itself and uses _launch)."""
+    with torch.cuda.device(dev):
+        _launch(dev, what, fn, *args)
+
+
+# The rows' forms of _f32c / _ptr (the rasterizer's above also turn an EMPTY tensor into None; a zero-size view has a non-null
+# data_ptr(), so the two are not interchangeable).
+def _row_f32c(t):
+    """fp32 and contiguous; the tensor itself when it already is"""
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def _row_ptr(t):
+    return None if t is None else t.data_ptr()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -627,21 +572,6 @@ class _RasterizeGaussians(torch.autograd.Function):
                         v(12, P2, 6) if cov_b.numel() else None)
 
 
-def _maps_lib():
-    """The library with the prototypes of the three map passes (hgs_maps_forward / _backward / _finish) set."""
-    lib = _load()
-    if getattr(lib, "_hgs_maps_ready", False):
-        return lib
-    lib.hgs_maps_forward.restype = C.c_int32
-    lib.hgs_maps_forward.argtypes = [C.POINTER(_ForwardArgs), C.POINTER(_ForwardState), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.hgs_maps_backward.restype = C.c_int32
-    lib.hgs_maps_backward.argtypes = [C.POINTER(_BackwardArgs), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.hgs_maps_finish.restype = C.c_int32
-    lib.hgs_maps_finish.argtypes = [C.POINTER(_BackwardArgs), C.c_void_p]
-    lib._hgs_maps_ready = True
-    return lib
-
-
 class _RasterizeGaussiansMaps(torch.autograd.Function):
     """_RasterizeGaussians with two more outputs behind its own: the accumulated-alpha map and the (un-normalised) depth map, both
     [1,H,W], from the frame's own lists (hgs_maps_forward) -- same inputs, scratch, hints, `second` and `clamp_output` handling.
@@ -651,7 +581,7 @@ class _RasterizeGaussiansMaps(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, clamp_output=False, *second):
-        lib = _maps_lib()
+        lib = _load()
         out = _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                           raster_settings, clamp_output, *second)
         dev = out[0].device
@@ -661,16 +591,13 @@ class _RasterizeGaussiansMaps(torch.autograd.Function):
         new = torch.zeros if P == 0 else torch.empty
         alpha, depth = (new(1, H, W, dtype=torch.float32, device=dev) for _ in range(2))
         if P > 0:
-            with torch.cuda.device(dev):
-                rc = lib.hgs_maps_forward(C.byref(ctx.bw.fwd), C.byref(ctx.bw.state), alpha.data_ptr(), depth.data_ptr(),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc < 0:
-                _raise_last(lib, "rasterize_gaussians (alpha and depth maps)")
+            _call(dev, "rasterize_gaussians (alpha and depth maps)", lib.hgs_maps_forward, C.byref(ctx.bw.fwd), C.byref(ctx.bw.state),
+                  alpha.data_ptr(), depth.data_ptr())
         return out + (alpha, depth)
 
     @staticmethod
     def backward(ctx, grad_out_color, *grads):
-        lib = _maps_lib()
+        lib = _load()
         grad_alpha, grad_depth = grads[-2], grads[-1]   # (in front of them: radii's and, with_visibility, the filter's None)
         saved = ctx.saved_tensors
         means3D = saved[0]
@@ -694,13 +621,11 @@ class _RasterizeGaussiansMaps(torch.autograd.Function):
             bw.dL_dout_color = grad_out_color.data_ptr()
             bw.flags = HGS_BWD_UPSTREAM_SCALE_GRAD if _UPSTREAM_SCALE_GRAD else 0
             with torch.cuda.device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                if with_maps and lib.hgs_maps_backward(C.byref(bw), _ptr(grad_alpha), _ptr(grad_depth), stream) < 0:
-                    _raise_last(lib, "rasterize_gaussians_backward (alpha and depth maps)")
-                if lib.hgs_rasterize_backward(C.byref(bw), stream) < 0:
-                    _raise_last(lib, "rasterize_gaussians_backward")
-                if with_maps and lib.hgs_maps_finish(C.byref(bw), stream) < 0:
-                    _raise_last(lib, "rasterize_gaussians_backward (alpha and depth maps)")
+                if with_maps:
+                    _launch(dev, "rasterize_gaussians_backward (alpha and depth maps)", lib.hgs_maps_backward, C.byref(bw), _ptr(grad_alpha), _ptr(grad_depth))
+                _launch(dev, "rasterize_gaussians_backward", lib.hgs_rasterize_backward, C.byref(bw))
+                if with_maps:
+                    _launch(dev, "rasterize_gaussians_backward (alpha and depth maps)", lib.hgs_maps_finish, C.byref(bw))
         return _RasterizeGaussians._input_grads(ctx, slab, saved)
 
 
@@ -890,11 +815,7 @@ class GaussianRasterizer(nn.Module):
             present = torch.zeros(P, dtype=torch.bool, device=positions.device)
             if P:
                 vm = _f32c(self.raster_settings.viewmatrix.to(positions.device))
-                with torch.cuda.device(positions.device):
-                    rc = lib.hgs_mark_visible(P, pos.data_ptr(), vm.data_ptr(), present.data_ptr(),
-                                              _stream_ptr(positions.device))
-                if rc < 0:
-                    _raise_last(lib, "mark_visible")
+                _call(positions.device, "mark_visible", lib.hgs_mark_visible, P, pos.data_ptr(), vm.data_ptr(), present.data_ptr())
         return present
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,

@@ -19,43 +19,17 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from diff_gaussian_rasterization import _aligned, _load, _raise_last, _require_gpu, _stream_ptr
+from diff_gaussian_rasterization import _aligned, _call, _load, _require_gpu
+from diff_gaussian_rasterization import _row_ptr as _ptr
+from diff_gaussian_rasterization._abi import MLP_MAX_HEADS as MAX_HEADS, MLP_MAX_TRUNK as MAX_TRUNK, _Desc, _Grads
 
-MAX_TRUNK, MAX_HEADS = 3, 3
 ACT_NONE, ACT_GELU, ACT_SIGMOID = 0, 1, 2
 _ACT_CODES = {None: ACT_NONE, "none": ACT_NONE, "gelu": ACT_GELU, "sigmoid": ACT_SIGMOID}
-_PROTO = False
-
-
-class _Desc(C.Structure):
-    _fields_ = [("in_width", C.c_int32), ("n_trunk", C.c_int32), ("trunk_width", C.c_int32 * MAX_TRUNK), ("n_heads", C.c_int32),
-                ("head_width", C.c_int32 * MAX_HEADS), ("head_act", C.c_int32 * MAX_HEADS),
-                ("trunk_weight", C.c_void_p * MAX_TRUNK), ("trunk_bias", C.c_void_p * MAX_TRUNK),
-                ("head_weight", C.c_void_p * MAX_HEADS), ("head_bias", C.c_void_p * MAX_HEADS)]
-
-
-class _Grads(C.Structure):
-    _fields_ = [("trunk_weight", C.c_void_p * MAX_TRUNK), ("trunk_bias", C.c_void_p * MAX_TRUNK),
-                ("head_weight", C.c_void_p * MAX_HEADS), ("head_bias", C.c_void_p * MAX_HEADS)]
-
-
-def _lib():
-    global _PROTO
-    lib = _load()
-    if not _PROTO:
-        lib.hgs_mlp_forward.restype = C.c_int32
-        lib.hgs_mlp_forward.argtypes = [C.c_int32, C.POINTER(_Desc), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
-        lib.hgs_mlp_backward.restype = C.c_int32
-        lib.hgs_mlp_backward.argtypes = [C.c_int32, C.POINTER(_Desc), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(_Grads), C.c_void_p]
-        lib.hgs_mlp_tile.restype = C.c_int32
-        lib.hgs_mlp_tile.argtypes = []
-        _PROTO = True
-    return lib
 
 
 def tile_points():
     """points per tile of the two kernels (tests choose their sizes around it)"""
-    return int(_lib().hgs_mlp_tile())
+    return int(_load().hgs_mlp_tile())
 
 
 def _describe(x, params, n_trunk, acts):
@@ -75,14 +49,11 @@ def _describe(x, params, n_trunk, acts):
 class _DecoderMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n_trunk, acts, *params):
-        lib = _lib()
+        lib = _load()
         n, dev = x.shape[0], x.device
         outs = tuple(torch.empty(n, params[2 * (n_trunk + k)].shape[0], dtype=torch.float32, device=dev) for k in range(len(acts)))
         desc = _describe(x, params, n_trunk, acts)
-        with torch.cuda.device(dev):
-            rc = lib.hgs_mlp_forward(n, C.byref(desc), x.data_ptr(), (C.c_void_p * MAX_HEADS)(*[o.data_ptr() for o in outs]), _stream_ptr(dev))
-        if rc < 0:
-            _raise_last(lib, "decoder_mlp")
+        _call(dev, "decoder_mlp", lib.hgs_mlp_forward, n, C.byref(desc), x.data_ptr(), (C.c_void_p * MAX_HEADS)(*[o.data_ptr() for o in outs]))
         ctx.set_materialize_grads(False)    # a head the loss does not use arrives as None and is skipped
         ctx.save_for_backward(x, *params)   # the inputs only: the hidden activations are recomputed
         ctx.n_trunk, ctx.acts = n_trunk, acts
@@ -92,7 +63,7 @@ class _DecoderMLP(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, *g_outs):
         x, *params = ctx.saved_tensors
-        lib = _lib()
+        lib = _load()
         n_trunk, acts = ctx.n_trunk, ctx.acts
         n, dev = x.shape[0], x.device
         g_outs = [None if g is None else _aligned(g) for g in g_outs]
@@ -100,18 +71,14 @@ class _DecoderMLP(torch.autograd.Function):
         # (the parameters of a head the loss does not use get None, as autograd gives a Linear outside the graph)
         used = lambda j: j < 2 * n_trunk or g_outs[(j - 2 * n_trunk) // 2] is not None
         d_params = [torch.zeros_like(p) if ctx.needs_input_grad[3 + j] and used(j) else None for j, p in enumerate(params)]
-        ptr = lambda t: None if t is None else t.data_ptr()
         grads = _Grads()
         for l in range(n_trunk):
-            grads.trunk_weight[l], grads.trunk_bias[l] = ptr(d_params[2 * l]), ptr(d_params[2 * l + 1])
+            grads.trunk_weight[l], grads.trunk_bias[l] = _ptr(d_params[2 * l]), _ptr(d_params[2 * l + 1])
         for k in range(len(acts)):
-            grads.head_weight[k], grads.head_bias[k] = ptr(d_params[2 * (n_trunk + k)]), ptr(d_params[2 * (n_trunk + k) + 1])
+            grads.head_weight[k], grads.head_bias[k] = _ptr(d_params[2 * (n_trunk + k)]), _ptr(d_params[2 * (n_trunk + k) + 1])
         desc = _describe(x, params, n_trunk, acts)
-        with torch.cuda.device(dev):
-            rc = lib.hgs_mlp_backward(n, C.byref(desc), x.data_ptr(), (C.c_void_p * MAX_HEADS)(*[ptr(g) for g in g_outs]), ptr(d_x),
-                                      C.byref(grads), _stream_ptr(dev))
-        if rc < 0:
-            _raise_last(lib, "decoder_mlp backward")
+        _call(dev, "decoder_mlp backward", lib.hgs_mlp_backward, n, C.byref(desc), x.data_ptr(), (C.c_void_p * MAX_HEADS)(*[_ptr(g) for g in g_outs]),
+              _ptr(d_x), C.byref(grads))
         return (d_x, None, None, *d_params)
 
 

@@ -11,11 +11,9 @@ Drop-in for the two statements that open `GaussianTrainer.scene_densification` /
 One HIP kernel instead of four boolean-indexed torch ops; same in-place semantics, including the reference's
 habit of pairing the FIRST n rows of the gradient with the model's n Gaussians.  No CPU fallback.
 """
-import ctypes as C
-
 import torch
 
-from diff_gaussian_rasterization import _load, _raise_last, _require_gpu, _stream_ptr
+from diff_gaussian_rasterization import _call, _load, _require_gpu
 
 
 def update_densification_stats(max_radii2D, xyz_gradient_accum, denom, viewspace_point_tensor, visibility_filter, radii):
@@ -34,10 +32,5 @@ def update_densification_stats(max_radii2D, xyz_gradient_accum, denom, viewspace
     vis = visibility_filter.contiguous().view(torch.uint8) if visibility_filter.dtype == torch.bool else \
         (visibility_filter != 0).contiguous().view(torch.uint8)
     rad = radii.to(torch.int32).contiguous()
-    lib.hgs_densification_stats.restype = C.c_int32
-    lib.hgs_densification_stats.argtypes = [C.c_int32] + [C.c_void_p] * 7
-    with torch.cuda.device(grad.device):
-        rc = lib.hgs_densification_stats(n, grad.data_ptr(), rad.data_ptr(), vis.data_ptr(), max_radii2D.data_ptr(),
-                                         xyz_gradient_accum.data_ptr(), denom.data_ptr(), _stream_ptr(grad.device))
-    if rc < 0:
-        _raise_last(lib, "densification_stats")
+    _call(grad.device, "densification_stats", lib.hgs_densification_stats, n, grad.data_ptr(), rad.data_ptr(), vis.data_ptr(),
+          max_radii2D.data_ptr(), xyz_gradient_accum.data_ptr(), denom.data_ptr())

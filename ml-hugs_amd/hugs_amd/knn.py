@@ -11,13 +11,13 @@ The search (and, for smpl_lbsweight_top_k -- the one on the every-training-step 
 function) runs in hand-written HIP (csrc/knn.hip) behind the C ABI; smpl_lbsmap_top_k keeps the reference's torch
 statements after the search because gradients flow through `verts_transform` there.  No CPU fallback.
 """
-import ctypes as C
 import os
 from collections import namedtuple
 
 import torch
 
-from diff_gaussian_rasterization import _aligned, _load, _raise_last, _require_gpu, _stream_ptr
+from diff_gaussian_rasterization import _aligned, _call, _launch, _load, _require_gpu
+from diff_gaussian_rasterization import _row_ptr as _ptr
 
 _KNN = namedtuple("KNN", "dists idx knn")   # pytorch3d's return type (knn is None unless return_nn=True)
 
@@ -33,8 +33,6 @@ def _prep(t, name):
 def _template_workspace(lib, n, m, device):
     """Scratch for the grid over the template (hgs_knn_workspace): with it the searches walk a few cells per point instead
     of scanning the whole template -- same neighbours, same order."""
-    lib.hgs_knn_workspace.restype = C.c_size_t
-    lib.hgs_knn_workspace.argtypes = [C.c_int32, C.c_int32]
     if os.environ.get("HGS_KNN_GRID", "1") == "0":            # A/B switch: the scan of the whole template
         return None
     nbytes = lib.hgs_knn_workspace(n, m)
@@ -48,8 +46,6 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, re
     if p1.ndim != 3 or p2.ndim != 3 or p1.shape[0] != p2.shape[0] or p1.shape[2] != 3 or p2.shape[2] != 3:
         raise ValueError("knn_points: expected p1 [B,n,3] and p2 [B,m,3]")
     lib = _load()
-    lib.hgs_knn_points_ws.restype = C.c_int32
-    lib.hgs_knn_points_ws.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     a, b = _prep(p1, "p1"), _prep(p2, "p2")
     B, n, m = a.shape[0], a.shape[1], b.shape[1]
     dists = torch.empty(B, n, K, dtype=torch.float32, device=a.device)
@@ -57,10 +53,8 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, re
     ws = _template_workspace(lib, n, m, a.device)
     with torch.cuda.device(a.device):
         for i in range(B):
-            rc = lib.hgs_knn_points_ws(n, a[i].data_ptr(), m, b[i].data_ptr(), K, dists[i].data_ptr(), idx[i].data_ptr(),
-                                       ws.data_ptr() if ws is not None else None, _stream_ptr(a.device))
-            if rc < 0:
-                _raise_last(lib, "knn_points")
+            _launch(a.device, "knn_points", lib.hgs_knn_points_ws, n, a[i].data_ptr(), m, b[i].data_ptr(), K, dists[i].data_ptr(),
+                    idx[i].data_ptr(), _ptr(ws))
     nn = None
     if return_nn:
         nn = torch.gather(p2[:, :, None, :].expand(-1, -1, K, -1), 1, idx[..., None].expand(-1, -1, -1, 3))
@@ -71,9 +65,6 @@ def smpl_lbsweight_top_k(lbs_weights, points, template_points, K=6):
     """-> (xyz_dist [B,n,1], xyz_neighbs_lbs_weight [B,n,J]); one fused kernel per batch element, no autograd (the
     reference's call sites wrap it in torch.no_grad() and its inputs' gradients are cut by the no_grad search)."""
     lib = _load()
-    lib.hgs_smpl_lbsweight_top_k_ws.restype = C.c_int32
-    lib.hgs_smpl_lbsweight_top_k_ws.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if points.ndim != 3 or template_points.ndim != 3 or lbs_weights.ndim != 2:
         raise ValueError("smpl_lbsweight_top_k: expected points [B,n,3], template_points [B,m,3], lbs_weights [m,J]")
     p, t, w = _prep(points, "points"), _prep(template_points, "template_points"), _prep(lbs_weights, "lbs_weights")
@@ -85,10 +76,8 @@ def smpl_lbsweight_top_k(lbs_weights, points, template_points, K=6):
     ws = _template_workspace(lib, n, m, p.device)
     with torch.cuda.device(p.device):
         for i in range(B):
-            rc = lib.hgs_smpl_lbsweight_top_k_ws(n, p[i].data_ptr(), m, t[i].data_ptr(), w.data_ptr(), J, K, dist[i].data_ptr(),
-                                                 out[i].data_ptr(), ws.data_ptr() if ws is not None else None, _stream_ptr(p.device))
-            if rc < 0:
-                _raise_last(lib, "smpl_lbsweight_top_k")
+            _launch(p.device, "smpl_lbsweight_top_k", lib.hgs_smpl_lbsweight_top_k_ws, n, p[i].data_ptr(), m, t[i].data_ptr(), w.data_ptr(),
+                    J, K, dist[i].data_ptr(), out[i].data_ptr(), _ptr(ws))
     return dist, out
 
 
@@ -108,9 +97,6 @@ class _LbsMapTopK(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lbs_weights, verts_transform, points, template_points, K, addition_info):
         lib = _load()
-        lib.hgs_smpl_lbsmap_top_k.restype = C.c_int32
-        lib.hgs_smpl_lbsmap_top_k.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                              C.c_void_p, C.c_int32] + [C.c_void_p] * 7
         p, t, w = _prep(points, "points"), _prep(template_points, "template_points"), _prep(lbs_weights, "lbs_weights")
         vt = _aligned(_prep(verts_transform.reshape(verts_transform.shape[0], 16), "verts_transform"))   # read as float4s
         info = _prep(addition_info, "addition_info") if addition_info is not None else None
@@ -123,13 +109,8 @@ class _LbsMapTopK(torch.autograd.Function):
         idx = torch.empty(n, K, dtype=torch.int32, device=dev)
         wgt = torch.empty(n, K, dtype=torch.float32, device=dev)
         ws = _template_workspace(lib, n, m, dev)
-        with torch.cuda.device(dev):
-            rc = lib.hgs_smpl_lbsmap_top_k(n, p.data_ptr(), m, t.data_ptr(), w.data_ptr(), J, K, vt.data_ptr(),
-                                           info.data_ptr() if info is not None else None, Cc, dist.data_ptr(), out_T.data_ptr(),
-                                           out_info.data_ptr() if info is not None else None, idx.data_ptr(), wgt.data_ptr(),
-                                           ws.data_ptr() if ws is not None else None, _stream_ptr(dev))
-        if rc < 0:
-            _raise_last(lib, "smpl_lbsmap_top_k")
+        _call(dev, "smpl_lbsmap_top_k", lib.hgs_smpl_lbsmap_top_k, n, p.data_ptr(), m, t.data_ptr(), w.data_ptr(), J, K, vt.data_ptr(),
+              _ptr(info), Cc, dist.data_ptr(), out_T.data_ptr(), _ptr(out_info), idx.data_ptr(), wgt.data_ptr(), _ptr(ws))
         ctx.save_for_backward(idx, wgt)
         ctx.dims = (n, K, m, Cc, tuple(verts_transform.shape), tuple(addition_info.shape) if addition_info is not None else None)
         ctx.mark_non_differentiable(dist)
@@ -138,9 +119,6 @@ class _LbsMapTopK(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _g_dist, g_T, g_info=None):
         lib = _load()
-        lib.hgs_smpl_lbsmap_top_k_backward.restype = C.c_int32
-        lib.hgs_smpl_lbsmap_top_k_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                                       C.c_void_p, C.c_void_p, C.c_void_p]
         idx, wgt = ctx.saved_tensors
         n, K, m, Cc, vt_shape, info_shape = ctx.dims
         dev = idx.device
@@ -151,13 +129,8 @@ class _LbsMapTopK(torch.autograd.Function):
         if need_T or need_info:
             gT = g_T.contiguous().float() if need_T else None
             gI = g_info.contiguous().float() if need_info else None
-            with torch.cuda.device(dev):
-                rc = lib.hgs_smpl_lbsmap_top_k_backward(n, K, idx.data_ptr(), wgt.data_ptr(), gT.data_ptr() if need_T else None,
-                                                        gI.data_ptr() if need_info else None, Cc,
-                                                        d_vt.data_ptr() if need_T else None, d_info.data_ptr() if need_info else None,
-                                                        _stream_ptr(dev))
-            if rc < 0:
-                _raise_last(lib, "smpl_lbsmap_top_k_backward")
+            _call(dev, "smpl_lbsmap_top_k_backward", lib.hgs_smpl_lbsmap_top_k_backward, n, K, idx.data_ptr(), wgt.data_ptr(), _ptr(gT),
+                  _ptr(gI), Cc, _ptr(d_vt), _ptr(d_info))
         return (None, d_vt.view(vt_shape) if need_T else None, None, None, None, d_info.view(info_shape) if need_info else None)
 
 
@@ -177,19 +150,11 @@ def distCUDA2(points):
     it and takes log(sqrt(.)) as the initial scale).  Exact: a brute-force scan for initialisation-sized clouds, a uniform
     grid search (same bits, O(n)) from 32 768 points on."""
     lib = _load()
-    lib.hgs_dist_cuda2_ws.restype = C.c_int32
-    lib.hgs_dist_cuda2_ws.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.hgs_dist_cuda2_workspace.restype = C.c_size_t
-    lib.hgs_dist_cuda2_workspace.argtypes = [C.c_int32]
     if points.ndim != 2 or points.shape[1] != 3:
         raise ValueError("distCUDA2: expected points [n,3]")
     p = _prep(points, "points")
     out = torch.empty(p.shape[0], dtype=torch.float32, device=p.device)
     nbytes = lib.hgs_dist_cuda2_workspace(p.shape[0])
     ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device) if nbytes else None
-    with torch.cuda.device(p.device):
-        rc = lib.hgs_dist_cuda2_ws(p.shape[0], p.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None,
-                                   _stream_ptr(p.device))
-    if rc < 0:
-        _raise_last(lib, "distCUDA2")
+    _call(p.device, "distCUDA2", lib.hgs_dist_cuda2_ws, p.shape[0], p.data_ptr(), out.data_ptr(), _ptr(ws))
     return out

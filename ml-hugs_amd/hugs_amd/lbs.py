@@ -14,42 +14,16 @@ hand-written HIP (csrc/lbs.hip) behind the C ABI; what stays in torch is what is
 pose-corrective matmul `pose_feature @ posedirs` (rocBLAS; every release config sets disable_posedirs: true) and
 batch_rodrigues in front of it.  No CPU fallback.
 """
-import ctypes as C
-
 import torch
 
-from diff_gaussian_rasterization import _aligned, _load, _raise_last, _require_gpu
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    lib = _load()
-    if not _bound:
-        p = C.c_void_p
-        lib.hgs_lbs_skin_forward.restype = C.c_int32
-        lib.hgs_lbs_skin_forward.argtypes = [C.c_int32, C.c_int32, p, p, p, p, p, p, p, p]
-        lib.hgs_lbs_skin_backward_workspace.restype = C.c_size_t
-        lib.hgs_lbs_skin_backward_workspace.argtypes = [C.c_int32, C.c_int32]
-        lib.hgs_lbs_skin_backward.restype = C.c_int32
-        lib.hgs_lbs_skin_backward.argtypes = [C.c_int32, C.c_int32] + [p] * 14
-        _bound = True
-    return lib
-
-
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+from diff_gaussian_rasterization import _aligned, _call, _load, _require_gpu
+from diff_gaussian_rasterization import _row_f32c as _f32c, _row_ptr as _ptr
 
 
 class _LbsSkin(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, weights, v, rotmat):
-        lib = _lib()
+        lib = _load()
         _require_gpu(v, "v")
         A, weights, v = _f32c(A.reshape(-1, 16)), _f32c(weights), _f32c(v)
         rotmat = None if rotmat is None else _f32c(rotmat.reshape(-1, 9))
@@ -60,11 +34,8 @@ class _LbsSkin(torch.autograd.Function):
         T = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
         verts = torch.empty(n, 3, dtype=torch.float32, device=dev)
         rot = torch.empty(n, 3, 3, dtype=torch.float32, device=dev) if rotmat is not None else None
-        with torch.cuda.device(dev):
-            rc = lib.hgs_lbs_skin_forward(n, J, A.data_ptr(), weights.data_ptr(), v.data_ptr(), _ptr(rotmat), T.data_ptr(),
-                                          verts.data_ptr(), _ptr(rot), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _raise_last(lib, "lbs_skin")
+        _call(dev, "lbs_skin", lib.hgs_lbs_skin_forward, n, J, A.data_ptr(), weights.data_ptr(), v.data_ptr(), _ptr(rotmat), T.data_ptr(),
+              verts.data_ptr(), _ptr(rot))
         ctx.save_for_backward(A, weights, v, T, *(() if rotmat is None else (rotmat,)))
         ctx.has_rot = rotmat is not None
         ctx.set_materialize_grads(False)
@@ -74,7 +45,7 @@ class _LbsSkin(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_verts, g_T, g_rot=None):
-        lib = _lib()
+        lib = _load()
         A, weights, v, T = ctx.saved_tensors[:4]
         rotmat = ctx.saved_tensors[4] if ctx.has_rot else None
         n, J = v.shape[0], A.shape[0]
@@ -87,12 +58,8 @@ class _LbsSkin(torch.autograd.Function):
         dv = torch.empty(n, 3, dtype=torch.float32, device=dev)
         dR = torch.empty(n, 3, 3, dtype=torch.float32, device=dev) if rotmat is not None else None
         ws = torch.empty(lib.hgs_lbs_skin_backward_workspace(n, J), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.hgs_lbs_skin_backward(n, J, A.data_ptr(), weights.data_ptr(), v.data_ptr(), _ptr(rotmat), T.data_ptr(),
-                                           _ptr(g_verts), _ptr(g_T), _ptr(g_rot), dA.data_ptr(), dW.data_ptr(), dv.data_ptr(),
-                                           _ptr(dR), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _raise_last(lib, "lbs_skin backward")
+        _call(dev, "lbs_skin backward", lib.hgs_lbs_skin_backward, n, J, A.data_ptr(), weights.data_ptr(), v.data_ptr(), _ptr(rotmat),
+              T.data_ptr(), _ptr(g_verts), _ptr(g_T), _ptr(g_rot), dA.data_ptr(), dW.data_ptr(), dv.data_ptr(), _ptr(dR), ws.data_ptr())
         return dA, dW, dv, dR
 
 

@@ -16,7 +16,6 @@ composites are formed while the tiles are loaded, none is written to memory), an
 
     from hugs_amd.losses import HumanSceneLoss           # instead of `from hugs.losses.loss import HumanSceneLoss`
 """
-import ctypes as C
 import os
 import weakref
 
@@ -24,29 +23,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from diff_gaussian_rasterization import _load, _raise_last, _require_gpu, _stream_ptr
-
-_PROTO = False
-
-
-def _lib():
-    global _PROTO
-    lib = _load()
-    if not _PROTO:
-        lib.hgs_ssim_l1_workspace.restype = C.c_size_t
-        lib.hgs_ssim_l1_workspace.argtypes = [C.c_int32] * 3
-        lib.hgs_ssim_l1_forward.restype = C.c_int32
-        lib.hgs_ssim_l1_forward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 6
-        lib.hgs_ssim_l1_backward.restype = C.c_int32
-        lib.hgs_ssim_l1_backward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 7
-        lib.hgs_masked_loss_workspace.restype = C.c_size_t
-        lib.hgs_masked_loss_workspace.argtypes = [C.c_int32] * 3
-        lib.hgs_masked_loss_forward.restype = C.c_int32
-        lib.hgs_masked_loss_forward.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 8
-        lib.hgs_masked_loss_backward.restype = C.c_int32
-        lib.hgs_masked_loss_backward.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 10
-        _PROTO = True
-    return lib
+from diff_gaussian_rasterization import _call, _load, _require_gpu
+from diff_gaussian_rasterization import _row_ptr as _ptr
 
 
 class _SsimL1(torch.autograd.Function):
@@ -56,17 +34,14 @@ class _SsimL1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, gt):
-        lib = _lib()
+        lib = _load()
         Cn, H, W = pred.shape
         need_grad = pred.requires_grad
         out = torch.empty(3, dtype=torch.float32, device=pred.device)
         maps = torch.empty(3, Cn, H, W, dtype=torch.float32, device=pred.device) if need_grad else None
         ws = torch.empty(lib.hgs_ssim_l1_workspace(Cn, H, W), dtype=torch.uint8, device=pred.device)
-        with torch.cuda.device(pred.device):
-            rc = lib.hgs_ssim_l1_forward(Cn, H, W, pred.data_ptr(), gt.data_ptr(), maps.data_ptr() if need_grad else None,
-                                         ws.data_ptr(), out.data_ptr(), _stream_ptr(pred.device))
-        if rc < 0:
-            _raise_last(lib, "ssim_l1_forward")
+        _call(pred.device, "ssim_l1_forward", lib.hgs_ssim_l1_forward, Cn, H, W, pred.data_ptr(), gt.data_ptr(), _ptr(maps), ws.data_ptr(),
+              out.data_ptr())
         ctx.save_for_backward(pred, gt, maps)
         return out
 
@@ -76,19 +51,15 @@ class _SsimL1(torch.autograd.Function):
         if hit is not None and hit[4] == id(ctx):  #  an entry that belongs to another graph stays)
             _LAST.pop("entry", None)
         pred, gt, maps = ctx.saved_tensors
-        lib = _lib()
+        lib = _load()
         Cn, H, W = pred.shape
         # d(l1 mean) = d(l1 sum) / (C H W): one device scalar for the kernel, no host round trip
         g = g.to(torch.float32)
         g_s = g[0:1].contiguous()
         g_l1 = (g[1:2] / float(Cn * H * W) + g[2:3]).contiguous()
         grad = torch.empty_like(pred)
-        with torch.cuda.device(pred.device):
-            rc = lib.hgs_ssim_l1_backward(Cn, H, W, pred.data_ptr(), gt.data_ptr(), maps.data_ptr() if maps is not None else None,
-                                          g_s.data_ptr() if g_s is not None else None, g_l1.data_ptr() if g_l1 is not None else None,
-                                          grad.data_ptr(), _stream_ptr(pred.device))
-        if rc < 0:
-            _raise_last(lib, "ssim_l1_backward")
+        _call(pred.device, "ssim_l1_backward", lib.hgs_ssim_l1_backward, Cn, H, W, pred.data_ptr(), gt.data_ptr(), _ptr(maps), g_s.data_ptr(),
+              g_l1.data_ptr(), grad.data_ptr())
         return grad, None
 
 
@@ -177,17 +148,13 @@ class _MaskedSsimL1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, gt, mask, bg, mode, need_grad):
-        lib = _lib()
+        lib = _load()
         Cn, H, W = pred.shape
         out = torch.empty(4, dtype=torch.float32, device=pred.device)
         maps = torch.empty(3, Cn, H, W, dtype=torch.float32, device=pred.device) if need_grad else None
         ws = torch.empty(lib.hgs_masked_loss_workspace(Cn, H, W), dtype=torch.uint8, device=pred.device)
-        with torch.cuda.device(pred.device):
-            rc = lib.hgs_masked_loss_forward(mode, Cn, H, W, pred.data_ptr(), gt.data_ptr(), mask.data_ptr(),
-                                             bg.data_ptr() if bg is not None else None, maps.data_ptr() if need_grad else None,
-                                             ws.data_ptr(), out.data_ptr(), _stream_ptr(pred.device))
-        if rc < 0:
-            _raise_last(lib, "masked_loss_forward")
+        _call(pred.device, "masked_loss_forward", lib.hgs_masked_loss_forward, mode, Cn, H, W, pred.data_ptr(), gt.data_ptr(), mask.data_ptr(),
+              _ptr(bg), _ptr(maps), ws.data_ptr(), out.data_ptr())
         ctx.mode = mode
         ctx.save_for_backward(pred, gt, mask, bg, maps, out)
         return out
@@ -195,17 +162,12 @@ class _MaskedSsimL1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         pred, gt, mask, bg, maps, out = ctx.saved_tensors
-        lib = _lib()
+        lib = _load()
         Cn, H, W = pred.shape
         g = g.to(torch.float32).contiguous()             # [dL/dl1, dL/dssim_term, .., ..]: two device scalars, read by the kernel
         grad = torch.empty_like(pred)
-        with torch.cuda.device(pred.device):
-            rc = lib.hgs_masked_loss_backward(ctx.mode, Cn, H, W, pred.data_ptr(), gt.data_ptr(), mask.data_ptr(),
-                                              bg.data_ptr() if bg is not None else None, maps.data_ptr() if maps is not None else None,
-                                              out.data_ptr(), g.data_ptr(), g.data_ptr() + 4,
-                                              grad.data_ptr(), _stream_ptr(pred.device))
-        if rc < 0:
-            _raise_last(lib, "masked_loss_backward")
+        _call(pred.device, "masked_loss_backward", lib.hgs_masked_loss_backward, ctx.mode, Cn, H, W, pred.data_ptr(), gt.data_ptr(),
+              mask.data_ptr(), _ptr(bg), _ptr(maps), out.data_ptr(), g.data_ptr(), g.data_ptr() + 4, grad.data_ptr())
         return grad, None, None, None, None, None
 
 

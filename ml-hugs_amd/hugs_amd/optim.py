@@ -22,31 +22,21 @@ import struct
 
 import torch
 
-from diff_gaussian_rasterization import _load, _raise_last, _require_gpu
+from diff_gaussian_rasterization import _call, _load, _require_gpu
+from diff_gaussian_rasterization._abi import _AdamTensor
 
-_bound = False
-_RECORD = struct.Struct("@PPPPq6f")   # hgs_adam_tensor: param, grad, exp_avg, exp_avg_sq, numel, 1 - b1, b2, 1 - b2, eps, step_size, bc2_sqrt
+# the table is packed with `struct` (one call per record) and handed over as an array of the mirror, _AdamTensor:
+# param, grad, exp_avg, exp_avg_sq, numel, 1 - b1, b2, 1 - b2, eps, step_size, bc2_sqrt
+_RECORD = struct.Struct("@PPPPq6f")
+assert _RECORD.size == C.sizeof(_AdamTensor) == 64
 _UNSUPPORTED = ("amsgrad", "maximize", "capturable", "differentiable")
 _layout_copies = 0
-
-
-def _lib():
-    global _bound
-    lib = _load()
-    if not _bound:
-        assert _RECORD.size == 64
-        lib.hgs_adam_step.restype = C.c_int32
-        lib.hgs_adam_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        lib.hgs_adam_limits.restype = None
-        lib.hgs_adam_limits.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        _bound = True
-    return lib
 
 
 def adam_limits():
     """(tensors per launch, elements per workgroup) of the kernel: launch-shape facts, results do not depend on them."""
     k, chunk = C.c_int32(0), C.c_int32(0)
-    _lib().hgs_adam_limits(C.byref(k), C.byref(chunk))
+    _load().hgs_adam_limits(C.byref(k), C.byref(chunk))
     return k.value, chunk.value
 
 
@@ -171,7 +161,7 @@ def _fused_step(optimizers):
         by_device = {}
         for r in recs:
             by_device.setdefault(r[0].device, []).append(r)
-        lib = _lib()
+        lib = _load()
         for dev, rs in by_device.items():
             buf = bytearray(_RECORD.size * len(rs))
             for i, (p, g, m, v, group, st) in enumerate(rs):
@@ -180,11 +170,8 @@ def _fused_step(optimizers):
                 lr = float(group["lr"])
                 _RECORD.pack_into(buf, i * _RECORD.size, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), 1.0 - b1, b2, 1.0 - b2,
                                   float(group["eps"]), lr / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t))
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                rc = lib.hgs_adam_step(C.addressof(C.c_char.from_buffer(buf)), len(rs), stream)
-            if rc < 0:   # validated before any launch: no tensor and no step count has moved
-                _raise_last(lib, "adam step")
+            # (validated before any launch: when this raises, no tensor and no step count has moved)
+            _call(dev, "adam step", lib.hgs_adam_step, (_AdamTensor * len(rs)).from_buffer(buf), len(rs))
             for r in rs:
                 st = r[5]
                 if torch.is_tensor(st["step"]):

@@ -8,29 +8,20 @@ Same signatures, any leading dimensions, same values and the same autograd gradi
 subgradient where a trace term is not positive, floor 0.1) -- one kernel per direction instead of ~15 / ~40 torch kernels, and
 none of the two boolean-mask indexing steps that make the reference wait for the device twice per call.  No CPU fallback.
 """
-import ctypes as C
-
 import torch
 
-from diff_gaussian_rasterization import _aligned, _load, _raise_last, _require_gpu, _stream_ptr
+from diff_gaussian_rasterization import _aligned, _call, _load, _require_gpu
 
 
-def _call(name, n, dev, *tensors):
-    lib = _load()
-    fn = getattr(lib, name)
-    fn.restype = C.c_int32
-    fn.argtypes = [C.c_int32] + [C.c_void_p] * (len(tensors) + 1)
-    with torch.cuda.device(dev):
-        rc = fn(n, *[t.data_ptr() for t in tensors], _stream_ptr(dev))
-    if rc < 0:
-        _raise_last(lib, name[4:])
+def _row(name, n, dev, *tensors):
+    _call(dev, name[4:], getattr(_load(), name), n, *[t.data_ptr() for t in tensors])
 
 
 class _MatrixToQuaternion(torch.autograd.Function):
     @staticmethod
     def forward(ctx, matrix):                                     # [n, 9] contiguous
         quat = torch.empty(matrix.shape[0], 4, dtype=torch.float32, device=matrix.device)
-        _call("hgs_matrix_to_quaternion", matrix.shape[0], matrix.device, matrix, quat)
+        _row("hgs_matrix_to_quaternion", matrix.shape[0], matrix.device, matrix, quat)
         ctx.save_for_backward(matrix)
         return quat
 
@@ -38,7 +29,7 @@ class _MatrixToQuaternion(torch.autograd.Function):
     def backward(ctx, g):
         (matrix,) = ctx.saved_tensors
         grad = torch.empty_like(matrix)
-        _call("hgs_matrix_to_quaternion_backward", matrix.shape[0], matrix.device, matrix, _aligned(g), grad)
+        _row("hgs_matrix_to_quaternion_backward", matrix.shape[0], matrix.device, matrix, _aligned(g), grad)
         return grad
 
 
@@ -46,7 +37,7 @@ class _Rotation6dToMatrix(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d6):                                         # [n, 6] contiguous
         matrix = torch.empty(d6.shape[0], 9, dtype=torch.float32, device=d6.device)
-        _call("hgs_rotation_6d_to_matrix", d6.shape[0], d6.device, d6, matrix)
+        _row("hgs_rotation_6d_to_matrix", d6.shape[0], d6.device, d6, matrix)
         ctx.save_for_backward(d6)
         return matrix
 
@@ -54,7 +45,7 @@ class _Rotation6dToMatrix(torch.autograd.Function):
     def backward(ctx, g):
         (d6,) = ctx.saved_tensors
         grad = torch.empty_like(d6)
-        _call("hgs_rotation_6d_to_matrix_backward", d6.shape[0], d6.device, d6, _aligned(g), grad)
+        _row("hgs_rotation_6d_to_matrix_backward", d6.shape[0], d6.device, d6, _aligned(g), grad)
         return grad
 
 

@@ -8,42 +8,23 @@ every training step, /root/reference/hugs/models/scene.py:147-160 --
 exp / normalize / sigmoid / cat in one HIP kernel, their backward in one more (the reference: 5 + ~17 torch kernels).  Same
 dict, same keys, same values (fp32: expf and the division by the norm are correctly rounded here as there).  No CPU fallback.
 """
-import ctypes as C
-
 import torch
 
-from diff_gaussian_rasterization import _aligned, _load, _raise_last, _require_gpu, _stream_ptr
-
-_PROTO = False
-
-
-def _lib():
-    global _PROTO
-    lib = _load()
-    if not _PROTO:
-        lib.hgs_scene_forward.restype = C.c_int32
-        lib.hgs_scene_forward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 10
-        lib.hgs_scene_backward.restype = C.c_int32
-        lib.hgs_scene_backward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 13
-        _PROTO = True
-    return lib
+from diff_gaussian_rasterization import _aligned, _call, _load, _ptr, _require_gpu
 
 
 class _SceneActivations(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling, rotation, opacity, features_dc, features_rest):
-        lib = _lib()
+        lib = _load()
         P, M = scaling.shape[0], 1 + features_rest.shape[1]
         dev = scaling.device
         scales, rotq = torch.empty_like(scaling), torch.empty_like(rotation)
         opac = torch.empty_like(opacity)
         shs = torch.empty(P, M, 3, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.hgs_scene_forward(P, M, scaling.data_ptr(), rotation.data_ptr(), opacity.data_ptr(), features_dc.data_ptr(),
-                                       features_rest.data_ptr() if M > 1 else None, scales.data_ptr(), rotq.data_ptr(),
-                                       opac.data_ptr(), shs.data_ptr(), _stream_ptr(dev))
-        if rc < 0:
-            _raise_last(lib, "scene_forward")
+        _call(dev, "scene_forward", lib.hgs_scene_forward, P, M, scaling.data_ptr(), rotation.data_ptr(), opacity.data_ptr(),
+              features_dc.data_ptr(), features_rest.data_ptr() if M > 1 else None, scales.data_ptr(), rotq.data_ptr(), opac.data_ptr(),
+              shs.data_ptr())
         ctx.save_for_backward(rotation, scales, opac)
         ctx.M = M
         ctx.set_materialize_grads(False)
@@ -52,20 +33,16 @@ class _SceneActivations(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_scales, g_rotq, g_opac, g_shs):
         rotation, scales, opac = ctx.saved_tensors
-        lib = _lib()
+        lib = _load()
         P, M, dev = scales.shape[0], ctx.M, scales.device
         c = _aligned
         g_scales, g_rotq, g_opac, g_shs = c(g_scales), c(g_rotq), c(g_opac), c(g_shs)
         new = lambda g, shape: torch.empty(shape, dtype=torch.float32, device=dev) if g is not None else None
         d_scaling, d_rot, d_op = new(g_scales, (P, 3)), new(g_rotq, (P, 4)), new(g_opac, (P, 1))
         d_dc, d_rest = new(g_shs, (P, 1, 3)), new(g_shs, (P, M - 1, 3))
-        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib.hgs_scene_backward(P, M, rotation.data_ptr(), scales.data_ptr(), opac.data_ptr(), ptr(g_scales), ptr(g_rotq),
-                                        ptr(g_opac), ptr(g_shs), ptr(d_scaling), ptr(d_rot), ptr(d_op), ptr(d_dc), ptr(d_rest),
-                                        _stream_ptr(dev))
-        if rc < 0:
-            _raise_last(lib, "scene_backward")
+        # (_ptr is the rasterizer's form: an empty tensor -- d_rest at M == 1 -- goes as NULL)
+        _call(dev, "scene_backward", lib.hgs_scene_backward, P, M, rotation.data_ptr(), scales.data_ptr(), opac.data_ptr(), _ptr(g_scales),
+              _ptr(g_rotq), _ptr(g_opac), _ptr(g_shs), _ptr(d_scaling), _ptr(d_rot), _ptr(d_op), _ptr(d_dc), _ptr(d_rest))
         return d_scaling, d_rot, d_op, d_dc, d_rest
 
 

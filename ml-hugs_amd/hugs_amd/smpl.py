@@ -19,32 +19,8 @@ from types import SimpleNamespace
 
 import torch
 
-from diff_gaussian_rasterization import _aligned, _load, _raise_last, _require_gpu
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    lib = _load()
-    if not _bound:
-        p, i = C.c_void_p, C.c_int32
-        lib.hgs_smpl_workspace.restype = C.c_size_t
-        lib.hgs_smpl_workspace.argtypes = [i, i, i]
-        lib.hgs_smpl_forward.restype = i
-        lib.hgs_smpl_forward.argtypes = [i, i, i, C.POINTER(i)] + [p] * 8 + [i] + [p] * 10
-        lib.hgs_smpl_backward.restype = i
-        lib.hgs_smpl_backward.argtypes = [i, i, i, C.POINTER(i)] + [p] * 5 + [i] + [p] * 15
-        _bound = True
-    return lib
-
-
-def _f32c(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+from diff_gaussian_rasterization import _aligned, _launch, _load, _require_gpu
+from diff_gaussian_rasterization import _row_f32c as _f32c, _row_ptr as _ptr
 
 
 def _host_parents(parents):
@@ -67,7 +43,7 @@ class _Smpl(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, betas, pose, transl, v_template, shapedirs, posedirs, J_regressor, lbs_weights, parents, disable_posedirs):
-        lib = _lib()
+        lib = _load()
         B, NB = betas.shape
         V, J = v_template.shape[0], J_regressor.shape[0]
         dev = betas.device
@@ -79,16 +55,12 @@ class _Smpl(torch.autograd.Function):
         ws = torch.empty(B, max(lib.hgs_smpl_workspace(V, J, NB), 16), dtype=torch.uint8, device=dev)
         pd = None if disable_posedirs else posedirs
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
             for b in range(B):
-                rc = lib.hgs_smpl_forward(V, J, NB, parents, betas[b].data_ptr(), pose[b].data_ptr(),
-                                          None if transl is None else transl[b].data_ptr(), v_template.data_ptr(), shapedirs.data_ptr(),
-                                          _ptr(pd), J_regressor.data_ptr(), lbs_weights.data_ptr(), int(disable_posedirs),
-                                          verts[b].data_ptr(), Jtr[b].data_ptr(), A[b].data_ptr(), T[b].data_ptr(), v_posed[b].data_ptr(),
-                                          v_shaped[b].data_ptr(), shape_offsets[b].data_ptr(), pose_offsets[b].data_ptr(),
-                                          ws[b].data_ptr(), stream)
-                if rc < 0:
-                    _raise_last(lib, "smpl lbs")
+                _launch(dev, "smpl lbs", lib.hgs_smpl_forward, V, J, NB, parents, betas[b].data_ptr(), pose[b].data_ptr(),
+                        None if transl is None else transl[b].data_ptr(), v_template.data_ptr(), shapedirs.data_ptr(),
+                        _ptr(pd), J_regressor.data_ptr(), lbs_weights.data_ptr(), int(disable_posedirs),
+                        verts[b].data_ptr(), Jtr[b].data_ptr(), A[b].data_ptr(), T[b].data_ptr(), v_posed[b].data_ptr(),
+                        v_shaped[b].data_ptr(), shape_offsets[b].data_ptr(), pose_offsets[b].data_ptr(), ws[b].data_ptr())
         ctx.save_for_backward(pose, shapedirs, J_regressor, lbs_weights, v_posed, T, ws, *(() if pd is None else (pd,)))
         ctx.parents, ctx.disable, ctx.has_transl, ctx.sizes = parents, bool(disable_posedirs), transl is not None, (B, V, J, NB)
         ctx.set_materialize_grads(False)
@@ -96,7 +68,7 @@ class _Smpl(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = _lib()
+        lib = _load()
         pose, shapedirs, J_regressor, lbs_weights, v_posed, T, ws = ctx.saved_tensors[:7]
         pd = None if ctx.disable else ctx.saved_tensors[7]
         B, V, J, NB = ctx.sizes
@@ -108,16 +80,12 @@ class _Smpl(torch.autograd.Function):
         g_verts, g_Jtr, g_A, g_T, g_vp, g_vs, g_so, g_po = grads
         g_T = _aligned(g_T)   # read as float4s, an element a whole number of them (the other seven gradients: scalar loads)
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
             for b in range(B):
                 at = lambda g: None if g is None else g[b].data_ptr()
-                rc = lib.hgs_smpl_backward(V, J, NB, ctx.parents, pose[b].data_ptr(), shapedirs.data_ptr(), _ptr(pd), J_regressor.data_ptr(),
-                                           lbs_weights.data_ptr(), int(ctx.disable), v_posed[b].data_ptr(), T[b].data_ptr(), at(g_verts),
-                                           at(g_Jtr), at(g_A), at(g_T), at(g_vp), at(g_vs), at(g_so), at(g_po), d_betas[b].data_ptr(),
-                                           d_pose[b].data_ptr(), None if d_transl is None else d_transl[b].data_ptr(), ws[b].data_ptr(),
-                                           stream)
-                if rc < 0:
-                    _raise_last(lib, "smpl lbs backward")
+                _launch(dev, "smpl lbs backward", lib.hgs_smpl_backward, V, J, NB, ctx.parents, pose[b].data_ptr(), shapedirs.data_ptr(),
+                        _ptr(pd), J_regressor.data_ptr(), lbs_weights.data_ptr(), int(ctx.disable), v_posed[b].data_ptr(), T[b].data_ptr(),
+                        at(g_verts), at(g_Jtr), at(g_A), at(g_T), at(g_vp), at(g_vs), at(g_so), at(g_po), d_betas[b].data_ptr(),
+                        d_pose[b].data_ptr(), None if d_transl is None else d_transl[b].data_ptr(), ws[b].data_ptr())
         return d_betas, d_pose, d_transl, None, None, None, None, None, None, None
 
 

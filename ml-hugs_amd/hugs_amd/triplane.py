@@ -16,24 +16,11 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from diff_gaussian_rasterization import _aligned, _load, _raise_last, _require_gpu, _stream_ptr
+from diff_gaussian_rasterization import _aligned, _call, _load, _require_gpu
+from diff_gaussian_rasterization import _row_ptr as _ptr
 
 EPS = 1e-3
 _FEATURES = 32
-_PROTO = False
-
-
-def _lib():
-    global _PROTO
-    lib = _load()
-    if not _PROTO:
-        lib.hgs_triplane_forward.restype = C.c_int32
-        lib.hgs_triplane_forward.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_float, C.c_float] + [C.c_void_p] * 6
-        lib.hgs_triplane_backward.restype = C.c_int32
-        lib.hgs_triplane_backward.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_float, C.c_float,
-                                              C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
-        _PROTO = True
-    return lib
 
 
 def _geometry(planes):
@@ -46,16 +33,13 @@ def _geometry(planes):
 class _TriplaneSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plane_xy, plane_xz, plane_yz, x, center, scale):
-        lib = _lib()
+        lib = _load()
         planes = (plane_xy, plane_xz, plane_yz)
         n, F, dev = x.shape[0], plane_xy.shape[1], x.device
         feat = torch.empty(n, 3 * F, dtype=torch.float32, device=dev)
         res, strides = _geometry(planes)
-        with torch.cuda.device(dev):
-            rc = lib.hgs_triplane_forward(n, F, res, strides, center, scale, x.data_ptr(), plane_xy.data_ptr(), plane_xz.data_ptr(),
-                                          plane_yz.data_ptr(), feat.data_ptr(), _stream_ptr(dev))
-        if rc < 0:
-            _raise_last(lib, "triplane_sample")
+        _call(dev, "triplane_sample", lib.hgs_triplane_forward, n, F, res, strides, center, scale, x.data_ptr(), plane_xy.data_ptr(),
+              plane_xz.data_ptr(), plane_yz.data_ptr(), feat.data_ptr())
         ctx.save_for_backward(plane_xy, plane_xz, plane_yz, x)
         ctx.center, ctx.scale = center, scale
         return feat
@@ -64,19 +48,15 @@ class _TriplaneSample(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_feat):
         *planes, x = ctx.saved_tensors
-        lib = _lib()
+        lib = _load()
         n, F, dev = x.shape[0], planes[0].shape[1], x.device
         g_feat = _aligned(g_feat)
         # zeroed with the PARAMETER's strides: the kernel adds into them through the same strides it reads the planes with
         d_planes = [torch.zeros_like(p, memory_format=torch.preserve_format) if ctx.needs_input_grad[i] else None for i, p in enumerate(planes)]
         d_x = torch.empty_like(x) if ctx.needs_input_grad[3] else None
         res, strides = _geometry(planes)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib.hgs_triplane_backward(n, F, res, strides, ctx.center, ctx.scale, x.data_ptr(), (C.c_void_p * 3)(*[p.data_ptr() for p in planes]),
-                                           g_feat.data_ptr(), ptr(d_x), (C.c_void_p * 3)(*[ptr(d) for d in d_planes]), _stream_ptr(dev))
-        if rc < 0:
-            _raise_last(lib, "triplane_sample backward")
+        _call(dev, "triplane_sample backward", lib.hgs_triplane_backward, n, F, res, strides, ctx.center, ctx.scale, x.data_ptr(),
+              (C.c_void_p * 3)(*[p.data_ptr() for p in planes]), g_feat.data_ptr(), _ptr(d_x), (C.c_void_p * 3)(*[_ptr(d) for d in d_planes]))
         return d_planes[0], d_planes[1], d_planes[2], d_x, None, None
 
 

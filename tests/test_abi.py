@@ -1,5 +1,6 @@
-"""CPU: the C-ABI library loads, exports every function include/hgs_rasterizer.h declares, its ctypes mirror has
-the C compiler's struct layout, and host-side validation errors come back through hgs_last_error().
+"""CPU: the C-ABI library loads, exports every function include/hgs_rasterizer.h declares, its ctypes mirror -- one table of
+prototypes and eight structs -- agrees with the header line by line and with the C compiler's layout field by field, and host-side
+validation errors come back through hgs_last_error().
 No compute call is made (there is no GPU here)."""
 import ctypes as C
 import os
@@ -31,39 +32,88 @@ def test_library_exports_every_declared_symbol():
     assert lib.hgs_abi_version() == header_version == dgr._ABI_VERSION
 
 
+def _declarations():
+    """{name: (return type, [parameter, ...])} of every function the header declares, as text: comments stripped, `type name(params);`."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*\b(hgs_\w+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+        assert name not in out, f"{name} is declared twice"
+        params = " ".join(params.split())
+        out[name] = (" ".join(ret.split()), [] if params == "void" else [p.strip() for p in params.split(",")])
+    return out
+
+
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "size_t": C.c_size_t, "float": C.c_float}
+
+
+def _check_parameter(decl, got, abi):
+    """The rule of diff_gaussian_rasterization/_abi.py for one parameter: `decl` is the header's text, `got` the table's ctypes type."""
+    words = [w for w in re.sub(r"[\*\[\]]", " ", decl).split() if w != "const"]
+    base = words[0]
+    if "*" not in decl and "[" not in decl:
+        return got is (abi._ALLOC_FN if base == "hgs_alloc_fn" else _SCALARS[base])
+    if base in abi.STRUCTS:
+        return got is C.POINTER(abi.STRUCTS[base])
+    return got in (C.c_void_p, C.c_char_p) or (isinstance(got, type) and issubclass(got, C._Pointer))
+
+
+def test_the_prototype_table_matches_the_header():
+    """Every line of PROTOTYPES against the declaration it mirrors: the same functions, return type, parameter count, and per position
+    the table's rule (scalars exact, pointers to mirrored structs typed, any other pointer or array some pointer type).  Needs no library."""
+    from diff_gaussian_rasterization import _abi
+    decls = _declarations()
+    assert len(decls) == len(_declared_functions()), sorted(set(_declared_functions()) - set(decls))   # a declaration the parser cannot read
+    assert set(decls) == set(_abi.PROTOTYPES), set(decls) ^ set(_abi.PROTOTYPES)
+    returns = dict(_SCALARS, **{"void": None, "const char *": C.c_char_p})
+    for name, (ret, params) in decls.items():
+        restype, argtypes = _abi.PROTOTYPES[name]
+        assert restype is returns[ret], f"{name}: returns {ret}, the table says {restype}"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters, the table has {len(argtypes)}"
+        for k, (decl, got) in enumerate(zip(params, argtypes)):
+            assert _check_parameter(decl, got, _abi), f"{name}: parameter {k} is `{decl}`, the table says {got}"
+
+
 def test_ctypes_structs_match_the_c_layout():
-    import diff_gaussian_rasterization as dgr
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "hgs_rasterizer.h"
-int main(void) {
-  printf("%zu %zu %zu %zu\n", sizeof(hgs_settings), sizeof(hgs_forward_args), sizeof(hgs_forward_state), sizeof(hgs_backward_args));
-  printf("%zu %zu %zu %zu\n", offsetof(hgs_forward_args, P), offsetof(hgs_forward_args, means3D), offsetof(hgs_forward_args, radii), offsetof(hgs_settings, campos));
-  printf("%zu %zu %zu %zu\n", offsetof(hgs_backward_args, state), offsetof(hgs_backward_args, dL_dout_color), offsetof(hgs_backward_args, grad_accum), offsetof(hgs_backward_args, dL_drotations));
-  /* ABI v6 / v7: the checkpoint buffer and the second segment */
-  printf("%zu %zu %zu %zu\n", sizeof(hgs_segment), offsetof(hgs_forward_args, backward_checkpoints), offsetof(hgs_forward_args, scratch_bytes), offsetof(hgs_forward_args, seg2));
-  printf("%zu %zu %zu %zu\n", offsetof(hgs_segment, cov3D_precomp), offsetof(hgs_forward_state, ckpt), offsetof(hgs_forward_state, n_token), offsetof(hgs_backward_args, seg2_dL_drotations));
-  printf("%zu %zu\n", offsetof(hgs_backward_args, flags), offsetof(hgs_forward_args, visible));
-  /* ABI v11: the other render's gradients to add, and the event the per-Gaussian kernel waits for */
-  printf("%zu %zu %zu\n", offsetof(hgs_backward_args, add_dL_dopacity), offsetof(hgs_backward_args, add_dL_drotations), offsetof(hgs_backward_args, wait_before_per_gaussian));
-  printf("%zu %zu %zu %zu\n", offsetof(hgs_forward_args, ckpt_slots_hint), offsetof(hgs_forward_state, ckpt_slots), offsetof(hgs_forward_state, ckpt_slots_used), offsetof(hgs_forward_args, before_wait_ctx));
-  return 0; }'''
+    """Every field of every mirrored struct: size of the struct, offset and size of the field, as the C compiler lays the header out."""
+    from diff_gaussian_rasterization import _abi
+    lines, want = [], []
+    for cname, mirror in _abi.STRUCTS.items():
+        lines.append(f'printf("%zu\\n", sizeof({cname}));')
+        want.append(C.sizeof(mirror))
+        for field, _ in mirror._fields_:
+            lines.append(f'printf("%zu %zu\\n", offsetof({cname}, {field}), sizeof((({cname} *)0)->{field}));')
+            want += [getattr(mirror, field).offset, getattr(mirror, field).size]
+    assert len(_abi.STRUCTS) == 8
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "hgs_rasterizer.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n"
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "t.c"), "w").write(prog)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
         out = subprocess.check_output([os.path.join(d, "t")]).decode().split()
-    v = list(map(int, out))
-    S, F, St, B = dgr._Settings, dgr._ForwardArgs, dgr._ForwardState, dgr._BackwardArgs
-    assert v[:4] == [C.sizeof(S), C.sizeof(F), C.sizeof(St), C.sizeof(B)]
-    assert v[4:8] == [F.P.offset, F.means3D.offset, F.radii.offset, S.campos.offset]
-    assert v[8:12] == [B.state.offset, B.dL_dout_color.offset, B.grad_accum.offset, B.dL_drotations.offset]
-    Sg = dgr._Segment
-    assert v[12:16] == [C.sizeof(Sg), F.backward_checkpoints.offset, F.scratch_bytes.offset, F.seg2.offset]
-    assert v[16:20] == [Sg.cov3D_precomp.offset, St.ckpt.offset, St.n_token.offset, B.seg2_dL_drotations.offset]
-    assert v[20:22] == [B.flags.offset, F.visible.offset]
-    assert v[22:25] == [B.add_dL_dopacity.offset, B.add_dL_drotations.offset, B.wait_before_per_gaussian.offset]
-    assert v[25:] == [F.ckpt_slots_hint.offset, St.ckpt_slots.offset, St.ckpt_slots_used.offset, F.before_wait_ctx.offset]
+    got = list(map(int, out))
+    names = [f"sizeof({c})" if f is None else f"{c}.{f} {what}" for c, m in _abi.STRUCTS.items()
+             for f, what in [(None, None)] + [(f, w) for f, _ in m._fields_ for w in ("offset", "size")]]
+    assert got == want, [(n, g, w) for n, g, w in zip(names, got, want) if g != w]
+    # hgs_alloc_fn: void *(*)(void *ctx, int buffer_id, size_t bytes)
+    assert _abi._ALLOC_FN._restype_ is C.c_void_p and _abi._ALLOC_FN._argtypes_ == (C.c_void_p, C.c_int, C.c_size_t)
+
+
+def test_prototypes_are_declared_in_the_table_only():
+    """No drift back: under ml-hugs_amd/, tests/ and tools/ nothing but the table module assigns a prototype of a function the header
+    declares (symbols of A/B and trace builds that the header does not declare are bound where they are used)."""
+    declared = set(_declared_functions())
+    assign = re.compile(r"(\w+)\s*\.\s*(?:argtypes|restype)\s*=[^=]")
+    found = []
+    for top in ("ml-hugs_amd", "tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                path = os.path.join(dirpath, f)
+                if not f.endswith(".py") or path.endswith(os.path.join("diff_gaussian_rasterization", "_abi.py")):
+                    continue
+                for k, line in enumerate(open(path).read().splitlines(), 1):
+                    for name in assign.findall(line):
+                        if name in declared or not name.startswith("hgs_"):   # (a variable may stand for any function)
+                            found.append(f"{os.path.relpath(path, ROOT)}:{k}: {name}")
+    assert not found, found
 
 
 def test_scratch_size_queries_and_offsets():
@@ -133,23 +183,14 @@ def test_widening_rows_reject_bad_arguments_through_the_c_abi():
     """The entry points' own checks (they return before any launch): sizes, null pointers, alignment."""
     import diff_gaussian_rasterization as dgr
     lib = dgr._load()
-    lib.hgs_last_error.restype = C.c_char_p
-    lib.hgs_ssim_l1_workspace.restype = C.c_size_t
-    lib.hgs_ssim_l1_workspace.argtypes = [C.c_int32] * 3
     assert lib.hgs_ssim_l1_workspace(3, 1080, 1920) == 8 * 3 * 30 * 68 and lib.hgs_ssim_l1_workspace(0, 4, 4) == 0
-    lib.hgs_ssim_l1_forward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 6
     assert lib.hgs_ssim_l1_forward(3, 0, 8, None, None, None, None, None, None) == -1 and b"ssim_l1_forward" in lib.hgs_last_error()
     assert lib.hgs_ssim_l1_forward(3, 8, 8, None, None, None, None, None, None) == -1 and b"null pointer" in lib.hgs_last_error()
-    lib.hgs_ssim_l1_backward.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 7
     assert lib.hgs_ssim_l1_backward(3, 8, 8, 16, 16, None, 16, None, 16, None) == -1 and b"needs forward's maps" in lib.hgs_last_error()
-    lib.hgs_scene_forward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 10
     assert lib.hgs_scene_forward(4, 0, *([None] * 10)) == -1 and lib.hgs_scene_forward(0, 16, *([None] * 10)) == 0
     assert lib.hgs_scene_forward(4, 16, 16, 20, 16, 16, 16, 16, 16, 16, 16, None) == -1 and b"16-byte aligned" in lib.hgs_last_error()
-    lib.hgs_matrix_to_quaternion.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.hgs_matrix_to_quaternion(-1, None, None, None) == -1 and lib.hgs_matrix_to_quaternion(0, None, None, None) == 0
     assert lib.hgs_matrix_to_quaternion(5, 16, 20, None) == -1
-    lib.hgs_knn_workspace.restype = C.c_size_t
-    lib.hgs_knn_workspace.argtypes = [C.c_int32, C.c_int32]
     assert lib.hgs_knn_workspace(110_210, 6890) > 0 and lib.hgs_knn_workspace(1000, 6890) == 0 and lib.hgs_knn_workspace(10_000, 100) == 0
 
 

@@ -233,14 +233,8 @@ def test_grid_search_equals_the_scan(K, layout, device):
     (ties: the lower index first) and a degenerate flat part.  Layouts: a normal cloud with sparse tails; a surface of
     human size (waves of one or two groups); queries spread evenly over the box (many groups per wave: the open list); every
     vertex on one line (a grid of one row)."""
-    import ctypes as C
     import diff_gaussian_rasterization as dgr
     lib = dgr._load()
-    lib.hgs_knn_workspace.restype = C.c_size_t
-    lib.hgs_knn_workspace.argtypes = [C.c_int32, C.c_int32]
-    args = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.hgs_knn_points.argtypes = args + [C.c_void_p]
-    lib.hgs_knn_points_ws.argtypes = args + [C.c_void_p, C.c_void_p]
     r = np.random.default_rng(K)
     templ, _, pts = body(30_000, 3445, 24, seed=40 + K)
     if layout == "surface":
@@ -283,15 +277,9 @@ def test_grid_search_equals_the_scan(K, layout, device):
 def test_grids_survive_non_finite_coordinates(device):
     """A template vertex / a cloud point at infinity (or NaN) leaves the bounding box without a cell size: the grid falls back to
     one cell and every finite query still gets the scan's answer."""
-    import ctypes as C
     import diff_gaussian_rasterization as dgr
     from hugs_amd.knn import distCUDA2
     lib = dgr._load()
-    lib.hgs_knn_workspace.restype = C.c_size_t
-    lib.hgs_knn_workspace.argtypes = [C.c_int32, C.c_int32]
-    args = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.hgs_knn_points.argtypes = args + [C.c_void_p]
-    lib.hgs_knn_points_ws.argtypes = args + [C.c_void_p, C.c_void_p]
     templ, _, pts = body(8000, 1500, 24, seed=77)
     for bad in (np.inf, -np.inf, np.nan):
         t = templ.copy()

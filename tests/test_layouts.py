@@ -133,20 +133,7 @@ def test_the_shared_aligned_copies_only_what_is_misaligned_or_strided():
 
 def _lib():
     import diff_gaussian_rasterization as dgr
-    lib = dgr._load()
-    p, i = C.c_void_p, C.c_int32
-    lib.hgs_last_error.restype = C.c_char_p
-    lib.hgs_lbs_skin_forward.restype = i
-    lib.hgs_lbs_skin_forward.argtypes = [i, i] + [p] * 8
-    lib.hgs_lbs_skin_backward.restype = i
-    lib.hgs_lbs_skin_backward.argtypes = [i, i] + [p] * 14
-    lib.hgs_smpl_forward.restype = i
-    lib.hgs_smpl_forward.argtypes = [i, i, i, C.POINTER(i)] + [p] * 8 + [i] + [p] * 10
-    lib.hgs_smpl_backward.restype = i
-    lib.hgs_smpl_backward.argtypes = [i, i, i, C.POINTER(i)] + [p] * 5 + [i] + [p] * 15
-    lib.hgs_smpl_lbsmap_top_k.restype = i
-    lib.hgs_smpl_lbsmap_top_k.argtypes = [i, p, i, p, p, i, i, p, p, i] + [p] * 7
-    return lib
+    return dgr._load()   # with the prototypes the wrappers call through (diff_gaussian_rasterization/_abi.py)
 
 
 INVALID = -1   # HGS_ERR_INVALID_ARGUMENT (include/hgs_rasterizer.h)

@@ -15,9 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _lib():
     import diff_gaussian_rasterization as dgr
-    lib = dgr._maps_lib()
-    lib.hgs_last_error.restype = C.c_char_p
-    return dgr, lib
+    return dgr, dgr._load()   # with the prototypes the binding calls through (diff_gaussian_rasterization/_abi.py)
 
 
 def test_every_function_the_header_declares_is_exported():

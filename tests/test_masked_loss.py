@@ -6,7 +6,6 @@ and runs it on CPU in fp32); the three entry points at the C boundary.
 GPU: the fused kernels, through the function and the module, against the restatement and the golden vectors, on every case and mode.
 Tolerances are tests/test_losses.py's: values 2e-5 * max(1, |value|), gradients 1e-4 of the largest entry (the reference's fp32 result
 and the restatement differ by at most 1.5e-7 relative in value and 1.4e-7 of the largest gradient entry: two orders of margin)."""
-import ctypes as C
 import functools
 import os
 
@@ -102,10 +101,7 @@ def test_the_cases_are_what_they_are_for():
 
 def _lib():
     import diff_gaussian_rasterization as dgr
-    from hugs_amd import losses
-    lib = losses._lib()
-    lib.hgs_last_error.restype = C.c_char_p
-    return dgr, lib
+    return dgr, dgr._load()   # with the prototypes the wrapper calls through (diff_gaussian_rasterization/_abi.py)
 
 
 def test_the_entry_points_are_exported_and_size_their_workspace():

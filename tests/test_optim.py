@@ -119,15 +119,19 @@ def test_construction_takes_the_references_forms_and_refuses_the_rest():
 
 
 def _lib():
+    import diff_gaussian_rasterization as dgr
     from hugs_amd import optim as O
-    lib = O._lib()
-    lib.hgs_last_error.restype = C.c_char_p
-    return lib, O._RECORD
+    return dgr._load(), O._RECORD   # with the prototypes the wrapper calls through (diff_gaussian_rasterization/_abi.py)
+
+
+def _table(buf):
+    """packed records as the array of hgs_adam_tensor mirrors the bound prototype takes"""
+    from diff_gaussian_rasterization._abi import _AdamTensor
+    return (_AdamTensor * (len(buf) // C.sizeof(_AdamTensor))).from_buffer(buf) if buf else None
 
 
 def _call(lib, n, blob):
-    buf = bytearray(blob)
-    return lib.hgs_adam_step(C.addressof(C.c_char.from_buffer(buf)) if buf else None, n, None)
+    return lib.hgs_adam_step(_table(bytearray(blob)), n, None)
 
 
 GOOD = (16, 32, 48, 64, 5, 0.1, 0.999, 0.001, 1e-15, 0.01, 0.03)
@@ -586,12 +590,12 @@ def test_a_rejected_table_launches_nothing(device, limits):
         for rec in recs:
             rec = tuple(p if r in GOOD[:4] else (p + r % 16 if r else 0) for p, r in zip(ptrs, rec[:4])) + rec[4:]
             buf = bytearray(head + R.pack(*rec))
-            rc = lib.hgs_adam_step(C.addressof(C.c_char.from_buffer(buf)), n, stream)
+            rc = lib.hgs_adam_step(_table(buf), n, stream)
             assert rc < 0 and what.encode() in lib.hgs_last_error(), (what, rec)
     torch.cuda.synchronize()
     assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(bufs, before))
     buf = bytearray(head + good(last))   # ... and the same table with a good last record runs
-    assert lib.hgs_adam_step(C.addressof(C.c_char.from_buffer(buf)), n, stream) == 0
+    assert lib.hgs_adam_step(_table(buf), n, stream) == 0
     torch.cuda.synchronize()
     assert all(not torch.equal(a[0], b[0]) for a, b in zip(bufs, before)) and all(torch.equal(a[1], b[1]) for a, b in zip(bufs, before))
 

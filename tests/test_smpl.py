@@ -169,16 +169,7 @@ def test_zero_pose_gives_identity_rotations_and_transforms():
 
 def _lib():
     import diff_gaussian_rasterization as dgr
-    lib = dgr._load()
-    p, i = C.c_void_p, C.c_int32
-    lib.hgs_last_error.restype = C.c_char_p
-    lib.hgs_smpl_workspace.restype = C.c_size_t
-    lib.hgs_smpl_workspace.argtypes = [i, i, i]
-    lib.hgs_smpl_forward.restype = i
-    lib.hgs_smpl_forward.argtypes = [i, i, i, C.POINTER(i)] + [p] * 8 + [i] + [p] * 10
-    lib.hgs_smpl_backward.restype = i
-    lib.hgs_smpl_backward.argtypes = [i, i, i, C.POINTER(i)] + [p] * 5 + [i] + [p] * 15
-    return lib
+    return dgr._load()   # with the prototypes the wrapper calls through (diff_gaussian_rasterization/_abi.py)
 
 
 def test_library_exports_the_three_entry_points():

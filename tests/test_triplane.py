@@ -68,14 +68,7 @@ def test_fp64_restatement_reproduces_the_reference_features_and_gradients():
 
 def _lib():
     import diff_gaussian_rasterization as dgr
-    lib = dgr._load()
-    lib.hgs_last_error.restype = C.c_char_p
-    lib.hgs_triplane_forward.restype = C.c_int32
-    lib.hgs_triplane_forward.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_float, C.c_float] + [C.c_void_p] * 6
-    lib.hgs_triplane_backward.restype = C.c_int32
-    lib.hgs_triplane_backward.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_float, C.c_float,
-                                          C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
-    return lib
+    return dgr._load()   # with the prototypes the wrapper calls through (diff_gaussian_rasterization/_abi.py)
 
 
 def test_library_exports_both_entry_points():

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
 """distCUDA2 (row f-4): the uniform-grid search against the brute-force scan, Gaussian clouds.  One JSON line."""
-import ctypes as C
 import json
 import os
 import sys
@@ -13,7 +12,6 @@ from hugs_amd.knn import distCUDA2              # noqa: E402
 
 dev = torch.device("cuda:0")
 lib = dgr._load()
-lib.hgs_dist_cuda2.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
 out = {}
 for n in (30_000, 100_000, 300_000, 1_000_000):
     p = torch.randn(n, 3, device=dev)

@@ -8,7 +8,6 @@ independent evaluation on the same GPU):
   * fused SceneGS.forward and rotation conversions == their torch statements.
     python tools/fuzz_rows.py [--seconds 60] [--seed 0]"""
 import argparse
-import ctypes as C
 import os
 import sys
 import time
@@ -118,9 +117,6 @@ def main():
     a = ap.parse_args()
     import diff_gaussian_rasterization as dgr
     lib = dgr._load()
-    lib.hgs_knn_workspace.restype = C.c_size_t
-    lib.hgs_knn_workspace.argtypes = [C.c_int32, C.c_int32]
-    lib.hgs_knn_points_ws.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     dev = torch.device("cuda:0")
     r = np.random.default_rng(a.seed)
     torch.manual_seed(a.seed)

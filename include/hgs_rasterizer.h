@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define HGS_ABI_VERSION 12
+#define HGS_ABI_VERSION 13
 
 /* scratch buffer ids passed to the allocation callback */
 enum { HGS_BUF_GEOM = 0, HGS_BUF_BINNING = 1, HGS_BUF_IMAGE = 2, HGS_BUF_CKPT = 3, HGS_NUM_BUFS = 4 };
@@ -555,6 +555,60 @@ typedef struct hgs_adam_tensor {
 int32_t hgs_adam_step(const hgs_adam_tensor *tensors, int32_t n, void *stream);
 /* Launch-shape facts for tests and wrappers (results do not depend on them): records per launch, elements per workgroup. */
 void hgs_adam_limits(int32_t *tensors_per_launch, int32_t *chunk_elems);
+
+/* SURVEY.md 8f row f-12 -- one densification round (clone, split, prune) of either model as a stream compaction:
+ * `densify_and_prune` of /root/reference/hugs/models/scene.py:325-458 and hugs/models/hugs_trimlp.py:733-878.  The final row list
+ * is a pure function of per-source-row predicates, so a round is a plan (classify + scan), ONE host readback of five counts
+ * (the caller allocates the results from them) and a multi-tensor scatter that reads every source row once.
+ *
+ * Plan.  g = xyz_gradient_accum / denom with NaN -> 0 (inf stays and is hot); m = max of the row's three scales, where
+ * scales = exp(scales[i]) for HGS_DENSIFY_SCENE (`scales` is _scaling) and scales[i] as given for HGS_DENSIFY_HUMAN (scales_canon);
+ * o = sigmoid(opacity[i]) for the scene, opacity[i] as given for the human.  With densify != 0:
+ *   clone  = |g| >= max_grad and m <= small_max
+ *   split  =  g  >= max_grad and m >  small_max  (human: and some (s - med) / med >= 1, med the middle one of the three scales)
+ *   pruned(o, r, b) = o < min_opacity or (use_screen and (r > max_screen_size or b > big_max))
+ *   the original stays   unless split or pruned(o, 0, m);   its clone is emitted when clone and not pruned(o, 0, m);
+ *   its two split copies are emitted when split and not pruned(o, 0, m'), m' = max(exp(log(scales / 1.6))) for the scene (the new
+ *   _scaling, activated again) and m for the human (scales_tmp is copied unchanged).  (The statistics are zero at prune time:
+ *   densification_postfix has reset them, hence r = 0.)
+ * With densify == 0 (the model is beyond max_n_gs): the original stays unless pruned(o, max_radii2D[i], m); nothing else is emitted.
+ * Output: kind[i] (bit 0 original stays, bit 1 clone emitted, bit 2 split copies emitted, bit 3 split-selected), per workgroup of
+ * hgs_densify_limits()'s rows_per_workgroup rows the exclusive prefix of its four counts in partials[4 * ceil(n / rows)] (the
+ * counts' scan is a second, single-workgroup launch: no workgroup waits for another), and
+ * totals[5] = { originals kept, clones, split copy 1, split copy 2, split-selected rows }.
+ * Result rows are ordered [originals kept | clones | split copy 1 | split copy 2], each in source order.
+ *
+ * Scatter.  Each record moves one [n, width] tensor into its [totals[0..3] summed, width] result by `mode`:
+ *   COPY             the row, to every emitted variant
+ *   MOMENT           the row for a kept original, zeros for clones and split copies (Adam's exp_avg / exp_avg_sq)
+ *   ZERO             zeros to every emitted row (src is not read and may be NULL)
+ *   XYZ_SPLIT        COPY, but split copy c of the k-th split-selected row gets  xyz + R (noise[c * totals[4] + k] * std):
+ *                    scene: R from rotation[i] (a quaternion w, x, y, z, normalised first), std = exp(scales[i]);
+ *                    human: R = rotation[i] (row-major 3x3), std = max(scales[i], 0).  Needs width 3 and scales, rotation, noise.
+ *   LOG_SCALE_SPLIT  COPY, split copies get log(exp(v) / 1.6)
+ *   DIV_SPLIT        COPY, split copies get v / 1.6
+ * A record of width 0 is skipped.  One launch per hgs_densify_limits()'s tensors_per_launch records, more records are chunked.
+ * kind, partials and totals are the plan's, untouched, and n, flavour the same; noise is [2 * totals[4], 3].
+ * Both validate before any launch (HGS_ERR_INVALID_ARGUMENT): n < 0, a null pointer with n > 0, an unknown flavour or mode,
+ * width < 0 or > 1024, count < 0 or beyond 16 launches' worth, XYZ_SPLIT without its three arrays or with width != 3.  n == 0:
+ * the plan writes zero totals, the scatter does nothing. */
+enum { HGS_DENSIFY_SCENE = 0, HGS_DENSIFY_HUMAN = 1 };
+enum { HGS_DENSIFY_COPY = 0, HGS_DENSIFY_MOMENT = 1, HGS_DENSIFY_ZERO = 2, HGS_DENSIFY_XYZ_SPLIT = 3, HGS_DENSIFY_LOG_SCALE_SPLIT = 4,
+       HGS_DENSIFY_DIV_SPLIT = 5 };
+typedef struct hgs_densify_tensor {
+    const float *src;        /* [n, width] */
+    float *dst;              /* [rows of the result, width] */
+    int32_t width;           /* floats per row */
+    int32_t mode;            /* HGS_DENSIFY_* */
+} hgs_densify_tensor;        /* 24 bytes */
+void hgs_densify_limits(int32_t *rows_per_workgroup, int32_t *tensors_per_launch);
+int32_t hgs_densify_plan(int32_t flavour, int32_t n, int32_t densify, const float *xyz_gradient_accum, const float *denom,
+                         const float *max_radii2D, const float *scales, const float *opacity, float max_grad, float min_opacity,
+                         float small_max, int32_t use_screen, float max_screen_size, float big_max, uint8_t *kind,
+                         uint32_t *partials, uint32_t *totals, void *stream);
+int32_t hgs_densify_scatter(int32_t flavour, int32_t n, const uint8_t *kind, const uint32_t *partials, const uint32_t *totals,
+                            const hgs_densify_tensor *tensors, int32_t count, const float *scales, const float *rotation,
+                            const float *noise, void *stream);
 
 /* Message for the last negative return value on the calling thread. */
 const char *hgs_last_error(void);

@@ -126,6 +126,9 @@ PROTOTYPES = {
     "hgs_smpl_backward": (i32, (i32, i32, i32, P(i32)) + (p,) * 5 + (i32,) + (p,) * 15),
     "hgs_adam_step": (i32, (P(_AdamTensor), i32, p)),
     "hgs_adam_limits": (None, (P(i32), P(i32))),
+    "hgs_densify_limits": (None, (P(i32), P(i32))),
+    "hgs_densify_plan": (i32, (i32, i32, i32) + (p,) * 5 + (f32, f32, f32, i32, f32, f32) + (p,) * 4),
+    "hgs_densify_scatter": (i32, (i32, i32, p, p, p, p, i32, p, p, p, p)),   # `tensors`: hgs_densify_tensor records, see hugs_amd/densify.py
     "hgs_last_error": (s, ()),
     "hgs_abi_version": (i32, ()),
     "hgs_geom_bytes": (sz, (i32, i32, i32)),
